@@ -30,9 +30,12 @@ and the folds over whole vectors stay replicated.  One IVC chain is sequential, 
 `--gpus N --threads` runs the same decomposition in ONE process, one host thread per GPU (srs_init_thread), partial sums exchanged in memory;
 `--gpus N --single-process` uses multi-device keys instead (the library owns the devices; the prove stays on device 0).
 
-Prints ONE JSON line (rank 0).  `roofline`: dominant kernel = MSM bucket accumulation; achieved = 96 B x scalars / launch time
-(HIP events on the launch stream, inside the library).  `cpu_baseline`: the CPU oracle (oracle/, a C port of the reference's
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps and prints the headline; everything else it used
+to measure beside the headline -- the roofline and per-kernel timers, the secondary objects, the CPU baseline, the N > 1 sharded MSM
+-- runs with `--full` only.  `roofline` (--full): dominant kernel = MSM bucket accumulation; achieved = 96 B x scalars / launch time
+(HIP events on the launch stream, inside the library).  `cpu_baseline` (--full): the CPU oracle (oracle/, a C port of the reference's
 algorithms -- the Rust reference cannot be built in this image) on ONE step of the same workload, rank 0 / N = 1 only.
+`--dump-outputs DIR` writes what the last timed step handed its caller as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -91,8 +94,14 @@ def parse():
     ap.add_argument("--leaf-rows", default="compat", choices=["true", "compat"],
                     help="ProtoGalaxy leaf row: row 0 like the reference (default: bit-exact with src/plonk/mod.rs:714, SURVEY.md Q1) "
                          "or the leaf's own row (`true`: the intended computation, reported as secondary.true_leaf_rows by default)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary objects (k=17 Sangria step, 2^24 MSM / NTT)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: roofline and per-kernel timers, the secondary objects and the CPU baseline (a plain run "
+                         "times the headline only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64, each 64-bit limb as two "
+                         "exact 32-bit words; vectors longer than 2^16 rows as a fixed, seeded sample of rows)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the secondary objects (k=17 Sangria step, 2^24 MSM / NTT)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--resident", action="store_true",
                     help="time the step with its inputs already in HBM (the new witness and the support trace are not uploaded inside the step): "
                          "what the default run reports as secondary.device_resident; the headline keeps the upload inside the step")
@@ -122,6 +131,9 @@ def parse():
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL, default) | gloo (CPU exchange; lets 2 ranks share one GPU in tests)")
     args = ap.parse_args()
     args.ro_challenge = args.challenges == "poseidon-ro" or args.ro_challenge
+    # a plain run is the headline alone: the secondary objects and the CPU baseline need --full
+    args.no_extras = args.no_extras or not args.full
+    args.no_cpu_baseline = args.no_cpu_baseline or not args.full
     return args
 
 
@@ -445,6 +457,7 @@ class PgPrimary:
         self.pending = None
         self.ro = S.PoseidonHash(0, 5, 4, 10, 10)
         self.step_no = 0
+        self.last = {}                # the dict the last prove returned
         self.dev_W, self.seen_C = None, {}
         self.page_W = None            # secondary.pageable_witness: plain (pageable) copies of the two host witnesses
 
@@ -499,6 +512,7 @@ class PgPrimary:
         pr = PG.prove(ctx, self.betas, delta_m, [self.accW, self.inW], ro=ro, alpha=None if ro else m([alpha])[0],
                       gamma=None if ro else m([gamma])[0], reference_compat=self.compat, fold=not defer)
         self.e, self.betas = pr["e"], pr["betas_stroke"]
+        self.last = pr                                # (what --dump-outputs writes)
         if defer:
             self.lag = pr["lagrange"]
         else:
@@ -547,6 +561,7 @@ class PgPrimary:
         # reference's row-0 leaves) -- srs_structure_fold_sharded
         PG.fold_witness(0, [self.accW, self.inW], lag, out=self.accW, structure=self.S, reference_compat=self.compat)
         self.betas = bs
+        self.last = dict(alpha=alpha_m, gamma=gamma_m, poly_F=pF, poly_K=pK, lagrange=lag)
         self.pending = S.point_lincomb_async(S.CURVE_BN256, None, np.stack([self.accC, self.inC]), lag[:2])       # fold_instance
 
     def witness_commit(self, S, D):
@@ -740,6 +755,91 @@ def nonzero_rows(t):
     return int((t != 0).any(dim=1).sum().item())
 
 
+# ------------------------------------------------------------------------------------------ --dump-outputs
+DUMP_ROWS = 1 << 16            # a longer vector is written as this many of its rows, drawn with a fixed seed
+DUMP_LIMIT = 64 * 10 ** 6      # bytes of all arrays of one dump
+
+
+def _words(x):
+    """field elements / points as the library hands them out (Montgomery form, 64-bit little-endian limbs), every limb as its two 32-bit
+    words in float64: exact, so that two builds compare bit for bit.  (..., L) limbs -> (..., 2 L) float64."""
+    if hasattr(x, "detach"):
+        x = x.detach().cpu().numpy()
+    return np.ascontiguousarray(x).view(np.uint64).view(np.uint32).astype(np.float64)
+
+
+def _rows(name, t, rows):
+    """(n, 4) vector -> (its words, None) or, above `rows` rows, (the words of a seeded sample of `rows` rows, the sorted row indices)"""
+    import zlib
+    n = t.shape[0]
+    if n <= rows:
+        return _words(t), None
+    idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(n, rows, replace=False))
+    if hasattr(t, "index_select"):
+        import torch
+        return _words(t.index_select(0, torch.from_numpy(idx).to(t.device))), idx
+    return _words(np.asarray(t)[idx]), idx
+
+
+def dump_outputs(path, scalars, vectors):
+    """--dump-outputs: scalars (name -> small array) are written whole, vectors (name -> (n, 4) array or tensor) through _rows, a
+    sample's row indices beside it as <name>_rows.npy.  The vectors share what the scalars leave of DUMP_LIMIT: at most DUMP_ROWS rows
+    each, fewer when many vectors would not fit (the scalars are bounded by the protocol -- the largest, poly_K, has at most 2^16
+    coefficients = 4 MiB of words).  The row count depends on the shapes alone, so the same arguments give the same dump.
+    -> what the result line reports about the dump."""
+    arrays = {name: _words(v) for name, v in scalars.items()}
+    left = DUMP_LIMIT - sum(a.nbytes for a in arrays.values())
+    per_row = 4 * 2 * 8 + 8                  # 4 limbs as 8 float64 words, + the row index of a sample
+    rows = min(DUMP_ROWS, max(left, 0) // (per_row * max(len(vectors), 1)))
+    for name, v in vectors.items():
+        arrays[name], idx = _rows(name, v, rows)
+        if idx is not None:
+            arrays[name + "_rows"] = idx.astype(np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {"dir": path, "arrays": len(arrays), "bytes": int(total)}
+
+
+def cyclefold_outputs(pri, sup, vectors):
+    """what the last CycleFold step handed its caller: the primary's prove (e, betas', F, K, alpha, gamma, the Lagrange values), folded
+    instance and new witness commitment, the support circuit's challenge and commitments; with `vectors` (one rank holds whole vectors)
+    also the folded primary witness, the device copy of the uploaded witness, the support accumulator (W, E) and its cross terms"""
+    pri.settle()
+    sup.settle()
+    pri.fold_done()
+    sc = {"primary_e": pri.e, "primary_betas": pri.betas, "primary_acc_commitment": pri.accC, "primary_incoming_commitment": pri.inC,
+          "support_acc_W_commitment": sup.accCW, "support_acc_E_commitment": sup.accCE, "support_incoming_commitment": sup.inC,
+          "support_r": sup.r}
+    sc.update({"primary_" + k: v for k, v in pri.last.items() if k in ("alpha", "gamma", "poly_F", "poly_K", "lagrange")})
+    keep = getattr(sup, "_keep", None)
+    if keep is not None:
+        sc["support_cross_term_commitments"] = keep["commits"]
+    vec = {}
+    if vectors:
+        vec = {"primary_acc_W": pri.accW, "primary_incoming_W": pri.inW, "support_acc_W": sup.accW, "support_acc_E": sup.accE}
+        if keep is not None:
+            vec.update({f"support_cross_term_{j}": t for j, t in enumerate(keep["terms"])})
+    return sc, vec
+
+
+def sangria_outputs(sides, vectors):
+    """what the last Sangria fold step handed its caller, per circuit: challenge, folded W / E commitments, the incoming trace's commitment
+    and the cross terms' commitments; with `vectors` also the folded accumulator (W, E)"""
+    sc, vec = {}, {}
+    for sd in sides:
+        sd.settle()
+        t = sd.tag
+        sc.update({f"{t}_acc_W_commitment": sd.accCW, f"{t}_acc_E_commitment": sd.accCE, f"{t}_incoming_commitment": sd.inC, f"{t}_r": sd.r})
+        keep = getattr(sd, "_keep", None)
+        if keep is not None:
+            sc[f"{t}_cross_term_commitments"] = keep["commits"]
+        if vectors:
+            vec.update({f"{t}_acc_W": sd.accW, f"{t}_acc_E": sd.accE})
+    return sc, vec
+
+
 # ------------------------------------------------------------------------------------------ CPU baselines (oracle/)
 def cpu_baseline_sangria(args, pri, sec, k):
     import oracle as O
@@ -824,7 +924,8 @@ def extras_sangria(S, D, args, k=17, log_key=21, steps=20, warmup=3):
     ro = args.ro_challenge
     sangria_step(S, D, pri, sec, False, ro, count=True)
     out = {"challenges": "poseidon-ro" if ro else "seeded"}
-    for name, from_host in (("device_resident", False), ("host_witness", True)):
+    legs = (("device_resident", False), ("host_witness", True)) if args.full else (("host_witness", True),)   # (host_witness: the headline of --config sangria)
+    for name, from_host in legs:
         gc_hold()
         for _ in range(warmup):
             sangria_step(S, D, pri, sec, from_host, ro)
@@ -837,10 +938,10 @@ def extras_sangria(S, D, args, k=17, log_key=21, steps=20, warmup=3):
             out["roofline"] = msm_roofline(S, "30 * 2^17 scalars per step over 2 batched launches (a trace and its cross terms each)", 16.0 * nz * steps / D.world, D.world)
             ct = S.profile_get("rowprog_cross_terms")
             out["cross_terms_ms_per_launch"] = round(ct["total_ms"] / ct["launches"], 4) if ct and ct["launches"] else None
-    # 1 counting step + (warmup + steps) x 2 legs, all on the same two accumulators: the digest of that chain (with Poseidon-derived r it
+    # 1 counting step + (warmup + steps) x the legs, all on the same two accumulators: the digest of that chain (with Poseidon-derived r it
     # equals tests/chain_cases.py::oracle_chain_sangria after the same number of steps; checked at k = 10 / 12 in tests/test_chain_gpu.py)
     out["state_digest"] = sangria_chain_digest(pri, sec)
-    out["steps_folded"] = 1 + 2 * (warmup + steps)
+    out["steps_folded"] = 1 + len(legs) * (warmup + steps)
     out["transcript"] = ("synthetic: r absorbs the accumulator's W / E commitments, the incoming W commitment and the cross-term commitments "
                          "(generate_challenge, src/nifs/sangria/mod.rs:162-179, without pp_digest / instances / u); the gate-compression "
                          "challenges and u of both instances are seeded constants")
@@ -1080,7 +1181,7 @@ def run(args, D):
         gc_hold()                  # (the collector runs here, BEFORE the warm-up steps, and stays off through the timed ones)
         for _ in range(args.warmup):
             cyclefold_step(S, D, pri, sup, args.ro_challenge, resident=resident)
-        S.profile_enable(True)
+        S.profile_enable(args.full)          # (the roofline's HIP events: --full only)
         S.profile_sampling(PROF_SAMPLE)
         S.profile_reset()
         dt = timed(D, lambda: cyclefold_step(S, D, pri, sup, args.ro_challenge, resident=resident), args.steps, after=lambda: (pri.settle(), sup.settle()))
@@ -1091,15 +1192,19 @@ def run(args, D):
         S.profile_sampling(1)
         scalars_per_step = pri.w["num_advice"] * pri.rows + (3 + 2) * sup.rows
         if D.rank == 0:
-            nz = sum(nonzero_rows(torch.from_numpy(hb.array.view(np.int64))) for hb in pri.host_W) / 2.0 + nonzero_rows(sup.inW) + sup.nz_terms
-            roof = msm_roofline(S, f"{pri.w['num_advice']}*2^{k} witness scalars in 10 chunks + the support circuit's 5*2^15 per step",
-                                16.0 * nz * args.steps / D.world if args.witness == "bench" else None, D.world,
-                                total_units=scalars_per_step * args.steps / D.world, sample_every=PROF_SAMPLE)
-            prof = {}
-            for name in ("pg_F_leaves", "pg_G_leaves", "rowprog_cross_terms"):
-                st = S.profile_get(name)
-                if st and st["launches"]:
-                    prof[name + "_ms"] = round(st["total_ms"] / st["launches"], 4)
+            dumped = None
+            if args.dump_outputs:
+                dumped = dump_outputs(args.dump_outputs, *cyclefold_outputs(pri, sup, D.world == 1))
+            roof, prof = None, {}
+            if args.full:
+                nz = sum(nonzero_rows(torch.from_numpy(hb.array.view(np.int64))) for hb in pri.host_W) / 2.0 + nonzero_rows(sup.inW) + sup.nz_terms
+                roof = msm_roofline(S, f"{pri.w['num_advice']}*2^{k} witness scalars in 10 chunks + the support circuit's 5*2^15 per step",
+                                    16.0 * nz * args.steps / D.world if args.witness == "bench" else None, D.world,
+                                    total_units=scalars_per_step * args.steps / D.world, sample_every=PROF_SAMPLE)
+                for name in ("pg_F_leaves", "pg_G_leaves", "rowprog_cross_terms"):
+                    st = S.profile_get(name)
+                    if st and st["launches"]:
+                        prof[name + "_ms"] = round(st["total_ms"] / st["launches"], 4)
             digest = chain_digest(pri, sup)
             out = {
                 "metric": "IVC fold-steps/s (CycleFold IVC::next hot path, Poseidon-shaped synthetic trace, 2^k rows)",
@@ -1125,8 +1230,12 @@ def run(args, D):
                                                 if D.multi else "single-gpu")},
                 "msm_scalars_per_s": round(scalars_per_step * args.steps / dt, 1),
                 "witness_upload_bytes_per_step": int(pri.w["num_advice"] * pri.rows * 32 + 3 * sup.rows * 32),
-                "roofline": roof, "kernel_ms": prof, "state_digest": digest,
+                "state_digest": digest,
             }
+            if args.full:
+                out["roofline"], out["kernel_ms"] = roof, prof
+            if dumped is not None:
+                out["dump_outputs"] = dumped
             if verify is not None:
                 out["verify"] = verify
             if resident:
@@ -1271,10 +1380,11 @@ def run(args, D):
     else:
         k = args.k or 17
         log_key = args.log_key or 21
-        S.profile_enable(True)
+        S.profile_enable(args.full)
         obj, cpu, sides = extras_sangria(S, D, args, k, log_key, args.steps, args.warmup)
         S.profile_enable(False)
         if D.rank == 0:
+            dumped = dump_outputs(args.dump_outputs, *sangria_outputs(sides, D.world == 1)) if args.dump_outputs else None
             main_leg = obj["host_witness"]
             out = {
                 "metric": "IVC fold-steps/s (Sangria, Poseidon-shaped synthetic trace, 2^k rows)",
@@ -1285,9 +1395,12 @@ def run(args, D):
                            "primary": "12 advice / 26 fixed / 2 gates / 6 cross terms", "secondary": "7 advice / 15 fixed / 1 gate / 5 cross terms",
                            "parallelism": f"msm-shard{D.world}" if D.world > 1 else "single-gpu"},
                 "msm_scalars_per_s": round(30 * (1 << k) * main_leg["fold_steps_per_s"], 1),
-                "device_resident_ms_per_step": obj["device_resident"]["ms_per_step"],
-                "roofline": obj["roofline"], "cross_terms_ms_per_launch": obj["cross_terms_ms_per_launch"],
             }
+            if args.full:
+                out.update({"device_resident_ms_per_step": obj["device_resident"]["ms_per_step"],
+                            "roofline": obj["roofline"], "cross_terms_ms_per_launch": obj["cross_terms_ms_per_launch"]})
+            if dumped is not None:
+                out["dump_outputs"] = dumped
             if cpu is not None:
                 out["cpu_baseline"] = cpu
     if D.rank == 0:

@@ -215,7 +215,7 @@ def test_bench_world2_matches_world1_on_emulator(tmp_path):
     env2 = {k: v for k, v in env.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     bench = [sys.executable, os.path.join(ROOT, "bench.py")]
     jobs = {"r1": (bench + ["--gpus", "1"] + common, env),
-            "r2": (bench + ["--gpus", "2", "--dist-backend", "gloo"] + [a for a in common if a != "--no-extras"], env2),
+            "r2": (bench + ["--gpus", "2", "--dist-backend", "gloo", "--full"] + [a for a in common if a != "--no-extras"], env2),
             "r1t": (bench + ["--gpus", "1", "--leaf-rows", "true"] + common, env),
             "r2t": (bench + ["--gpus", "2", "--dist-backend", "gloo", "--leaf-rows", "true"] + common, env2),
             "r3s": (bench + ["--gpus", "3", "--single-process"] + common, env2),       # one process, multi-device keys of 3 logical shards

@@ -288,11 +288,11 @@ def _commit_upload_and_multi_device_key(emu, O):
 
 def test_emu_bench_harness():
     """bench.py end to end on the emulator (tiny sizes): the harness logic -- CycleFold step order, host witness buffers,
-    commit_upload with a device copy, the CPU-baseline leg -- produces the JSON line with the contract's fields."""
+    commit_upload with a device copy, the CPU-baseline leg (--full) -- produces the JSON line with the contract's fields."""
     import json
     import sys
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--emu", "--k", "3", "--log-key", "7", "--steps", "1", "--warmup", "0",
-                        "--cpu-threads", "2", "--verify"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                        "--cpu-threads", "2", "--verify", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     # the secondary lines run too (tiny sizes); device_resident asserts inside bench.py that every resident commit == the streamed commit of the same witness
@@ -318,6 +318,84 @@ def test_emu_bench_resident_chain():
         lines[tag] = json.loads(r.stdout.strip().splitlines()[-1])
     assert lines["host"]["state_digest"] == lines["resident"]["state_digest"]
     assert "inputs" in lines["resident"]["config"] and "inputs" not in lines["host"]["config"]
+
+
+# bench.py through a driver that counts CycleFold steps: all of them, and those inside each timed region (bench.timed)
+COUNTING_BENCH = (
+    "import json, sys\n"
+    "sys.path.insert(0, sys.argv[1])\n"
+    "import bench\n"
+    "steps, timed_steps = [0], []\n"
+    "step, timed = bench.cyclefold_step, bench.timed\n"
+    "def counted_step(*a, **kw):\n"
+    "    steps[0] += 1\n"
+    "    return step(*a, **kw)\n"
+    "def counted_timed(D, fn, n, after=None):\n"
+    "    before = steps[0]\n"
+    "    dt = timed(D, fn, n, after)\n"
+    "    timed_steps.append(steps[0] - before)\n"
+    "    return dt\n"
+    "bench.cyclefold_step, bench.timed = counted_step, counted_timed\n"
+    "sys.argv = ['bench.py'] + sys.argv[2:]\n"
+    "bench.main()\n"
+    "print('COUNTS ' + json.dumps({'steps': steps[0], 'timed': timed_steps}))\n")
+
+
+def test_emu_bench_plain_run_and_dump(tmp_path):
+    """A plain bench.py run (no --full) times the headline alone: the contract's fields, exactly `--steps` CycleFold steps inside the one
+    timed region (counted by a driver that wraps bench.cyclefold_step) and none of --full's objects.  --dump-outputs writes what the last
+    timed step computed: a run of bench.py and one through the counting driver, with the same arguments, write the same arrays, and the
+    arrays `state_digest` hashes, put back together from their 32-bit words, give the line's digest."""
+    import hashlib
+    import json
+    import sys
+    subprocess.check_call(["make", "-C", EMU_DIR, "-j4"], stdout=subprocess.DEVNULL)
+    args = ["--emu", "--k", "3", "--log-key", "7", "--steps", "3", "--warmup", "1"]
+    res = _run_all([("a", [sys.executable, os.path.join(ROOT, "bench.py")] + args + ["--dump-outputs", str(tmp_path / "a")], dict(os.environ)),
+                    ("b", [sys.executable, "-c", COUNTING_BENCH, ROOT] + args + ["--dump-outputs", str(tmp_path / "b")], dict(os.environ))])
+    lines = {}
+    for tag, r in res.items():
+        assert r.returncode == 0, (tag, r.stderr[-2000:])
+        lines[tag] = json.loads([l for l in r.stdout.strip().splitlines() if l.startswith("{")][-1])
+    counts = json.loads([l for l in res["b"].stdout.splitlines() if l.startswith("COUNTS ")][-1][len("COUNTS "):])
+    assert counts == {"steps": 1 + 1 + 3, "timed": [3]}, counts      # the untimed first step of the chain + warm-up + timed steps
+    a, b = lines["a"], lines["b"]
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in a, key
+    assert a["steps"] == b["steps"] == 3 and a["unit"] == "fold-steps/s" and a["higher_is_better"] is True
+    assert abs(a["value"] * a["ms_per_step"] / 1e3 - 1.0) < 1e-2            # steps / s and ms per step of the same timed region
+    assert not {"roofline", "kernel_ms", "secondary", "cpu_baseline", "summary"} & set(a)
+    assert a["state_digest"] == b["state_digest"]
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == sorted(p.name for p in (tmp_path / "b").iterdir()) and len(names) == a["dump_outputs"]["arrays"]
+    for name in names:
+        x, y = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert x.dtype == np.float64 and np.array_equal(x, y), name
+    limbs = lambda name: np.load(tmp_path / "a" / (name + ".npy")).astype(np.uint32).view(np.uint64)
+    hashed = ("primary_e", "primary_acc_commitment", "primary_incoming_commitment", "support_acc_W_commitment", "support_acc_E_commitment",
+              "support_incoming_commitment")
+    assert hashlib.sha256(b"".join(limbs(n).tobytes() for n in hashed)).hexdigest() == a["state_digest"]
+
+
+def test_bench_dump_shrinks_to_its_limit(tmp_path):
+    """bench.dump_outputs: when every long vector at DUMP_ROWS rows would exceed DUMP_LIMIT, the vectors share the budget (fewer sampled
+    rows each) instead of aborting the run; the sample is the same for the same shapes, its row indices are sorted, distinct and in range,
+    and the written words are exactly the sampled rows."""
+    import bench
+    rng = np.random.default_rng(9)
+    small = {"c": rng.integers(0, 1 << 63, size=(2, 8), dtype=np.uint64)}
+    v = rng.integers(0, 1 << 63, size=(100_000, 4), dtype=np.uint64)
+    vectors = {f"v{i}": v for i in range(16)}                   # 16 x 2^16 sampled rows would be 75 MB
+    info = [bench.dump_outputs(str(tmp_path / t), small, vectors) for t in ("a", "b")]
+    assert info[0]["bytes"] <= bench.DUMP_LIMIT and info[0]["arrays"] == 1 + 2 * len(vectors)
+    assert sum(np.load(p).nbytes for p in (tmp_path / "a").iterdir()) == info[0]["bytes"]
+    for name in vectors:
+        w, idx = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "a" / f"{name}_rows.npy").astype(np.int64)
+        assert 0 < len(idx) < bench.DUMP_ROWS and w.shape == (len(idx), 8)
+        assert np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < v.shape[0]
+        assert np.array_equal(w.astype(np.uint32).view(np.uint64), v[idx])
+        assert np.array_equal(w, np.load(tmp_path / "b" / f"{name}.npy"))
+    assert np.array_equal(np.load(tmp_path / "a" / "c.npy").astype(np.uint32).view(np.uint64), small["c"])
 
 
 def test_emu_commit_vs_eip196():

@@ -10,6 +10,6 @@ print('$2', 'ms/step', d['ms_per_step'], 'accum0 avg ms', r.get('avg_launch_ms')
 for round in $(seq 1 ${2:-2}); do
   for lib in "" $R/variants/*.so; do
     tag=$(basename "${lib:-main}" .so)
-    SRS_AMD_LIB=$lib python bench.py --no-extras --no-cpu-baseline --steps 20 --warmup 5 > $O/c20_${tag}_$round.json 2>$O/c20_${tag}_$round.err; pick $O/c20_${tag}_$round.json "k20 $tag #$round"
+    SRS_AMD_LIB=$lib python bench.py --full --no-extras --no-cpu-baseline --steps 20 --warmup 5 > $O/c20_${tag}_$round.json 2>$O/c20_${tag}_$round.err; pick $O/c20_${tag}_$round.json "k20 $tag #$round"
   done
 done

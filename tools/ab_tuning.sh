@@ -6,7 +6,7 @@ for round in $(seq 1 $rounds); do
   for spec in "$@"; do
     set -- $spec; name=$1; lib=$2; tun=$3
     [ "$lib" = "-" ] && lib=""; [ "$tun" = "-" ] && tun=""
-    SRS_TEST_TUNING=$tun SRS_AMD_LIB=${lib:+$R/$lib} python bench.py --no-extras --no-cpu-baseline --steps 20 --warmup 5 > $O/$name.$round.json 2>$O/$name.$round.err
+    SRS_TEST_TUNING=$tun SRS_AMD_LIB=${lib:+$R/$lib} python bench.py --full --no-extras --no-cpu-baseline --steps 20 --warmup 5 > $O/$name.$round.json 2>$O/$name.$round.err
     python -c "
 import json
 d=json.loads(open('$O/$name.$round.json').read().strip().splitlines()[-1])

@@ -1,5 +1,6 @@
 """bench.py's own device-resident leg with per-step times on stderr (a patched COPY of bench.py is executed; diagnosis of the 13 ms that
-`secondary.device_resident` reads after --steps 10).  usage: python tools/resident_in_bench.py [bench.py arguments]"""
+`secondary.device_resident` reads after --steps 10; the leg runs with --full, which is passed on).  usage: python tools/resident_in_bench.py
+[bench.py arguments]"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 src = open(os.path.join(ROOT, "bench.py")).read()
@@ -24,5 +25,5 @@ new = """                import torch as _t, gc as _gc
 """
 assert src.count(old) == 1
 src = src.replace(old, new).replace('ROOT = os.path.dirname(os.path.abspath(__file__))', 'ROOT = %r' % ROOT)
-sys.argv = ["bench.py"] + sys.argv[1:]
+sys.argv = ["bench.py", "--full"] + [a for a in sys.argv[1:] if a != "--full"]
 exec(compile(src, os.path.join(ROOT, "bench.py"), "exec"), {"__name__": "__main__", "__file__": os.path.join(ROOT, "bench.py")})
