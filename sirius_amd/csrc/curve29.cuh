@@ -209,7 +209,8 @@ struct Ec29 {
     // x coordinates (Q = +-acc) are not handled but DETECTED: `exc` is set and the caller recomputes its whole chain with madd_signed
     // (one sticky flag per chain instead of two operand tests, a branch and the doubling path inside every addition: VERDICT r05 item 2).
     // The value returned in an exceptional case is garbage within the limb bounds (every intermediate keeps its stated bound whatever
-    // the operands hold, so nothing overflows before the chain is redone).
+    // the operands hold, so nothing overflows before the chain is redone; tests/field29_cases.py, `chainf_raw`: the returned limbs and values
+    // after every kind of exception and after two further additions, on the host and on the GPU).
     //   Q = O   <=>  y == 0 (no point of a curve of odd order has y = 0; the table's identity is (0, 0))
     //   acc = O <=>  zz == 0 exactly; it makes u2 = 0, p = -X1 ...: not detected by pp -- tested on its own
     SRS_HD static xyzz29_t madd_signed_fast(const xyzz29_t &a, const aff29_t &q, bool neg, bool &exc) {

@@ -167,6 +167,15 @@ struct Fp {
     // product, no zero-extension moves (a C CIOS form compiles to 575 instructions, 250 of them
     // v_mov; this form to 405).  Measured rates: profiles/r01_ubench_gfx950*.txt.
     // Host (and the CPU logic emulator): portable 4x64 CIOS, identical results.
+    //
+    // Operand domain (both bodies): a * b < 2^256 * p with a < 2^255 and b < 2^256 -- canonical operands, operands in [p, 2p) on
+    // either or both sides (4 p^2 < 2^256 p), and any 256-bit b against an a small enough (from_mont: b = 1; to_mont of a raw word).
+    // Both compute t = (a b + m p) / 2^256 with m < 2^256 exactly, so t < a b / 2^256 + p < 2p, drop nothing above bit 255 and
+    // reduce once: the result is canonical.  Outside a b < 2^256 p the sum reaches 2p and more and one subtraction no longer
+    // reduces it (and past 2^256 its top bit is dropped).  The device body is symmetric in a and b (a column is at most 8 + 8
+    // products below 2^64 plus a carry below 2^37, far inside its 96 bits); the host body keeps its running sum below a + p, which
+    // is why a < 2^255 is asked for: every row sum t + a * b_i then stays below 2^320, the five words it has.  Checked on exactly
+    // this domain by tests/test_field29_host.py (host body) and tests/test_field29_gpu.py (device body), same vectors.
 #if defined(__HIP_DEVICE_COMPILE__)
     static __device__ __forceinline__ fe_t mul(const fe_t &a, const fe_t &b) {
 #include "field_fips.inc"

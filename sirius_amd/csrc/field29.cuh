@@ -127,6 +127,8 @@ struct Fp29 {
     // operand of v_mad_u64_u32) -- hipcc builds the next column's sum on the side and joins the two with a v_lshl_add_u64 per column (16
     // per product, 144 per mixed addition, 4.2 cycles each).  Same values, same bounds.  Generated (tools/gen_field29_chain.py): one asm
     // statement per run of multiply-accumulates, because every statement costs an s_nop.
+    // "Same values, same bounds" is checked word for word: tests/test_field29_gpu.py runs these bodies on the GPU (tests/devcalc) and
+    // the C++ ones below on the host (tests/test_field29_host.py) on one set of vectors at the limb, value and column-sum bounds.
 #include "field29_chain.inc"
 #else
     // Montgomery product a * b / 2^261 mod p -- see the bounds in the header comment

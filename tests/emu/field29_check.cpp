@@ -2,10 +2,13 @@
 // A line-oriented calculator: tests/test_field29_host.py feeds operands chosen at the stated bounds of the lazy 9 x 29-bit
 // arithmetic and checks every result with Python integers.
 //   mul F a[9] b[9] | sqr F a[9] | norm F a[9] | add F a[9] b[9] | sub F CP E a[9] b[9] | neg F CP E b[9] | canon F a[9]
-//   unpack F w[8] | pack F a[9]
+//   unpack F w[8] | pack F a[9] | redlazy F a[9]
+//   mul8 F a[8] b[8]             : Fp<P>::mul on the 8 x 32-bit form (here the host 4 x 64 CIOS; on the device the generated FIPS body)
 //   mul2 F a[9] b[9] c[9] d[9]   : (a b + c d) / 2^261 with one reduction
 //   chain C n (w[16] neg){n}     : identity + n mixed additions of table-form points, lazy in between -> packed XYZZ (32 words)
 //   chains C n (w[16] neg){n}    : the same through madd_signed / load_raw (what k_accum0 runs)
+//   chainf C has_init [init[32]] n (w[16] neg){n} : the chain as accumulate_part runs it (field29_calc.h: calc_chainf), n >= 1 -> packed + exc
+//   chainf_raw ...               : the same, printing the unpacked 4 x 9 limbs (x y zz zzz) + exc: the bounds of the "garbage" after an exception
 //   addp C a[32] b[32]           : Ec29::add of two packed partial sums -> packed
 //   dblp C a[32]                 : Ec29::dbl -> packed
 //   tform C w[16]                : table_form of an ABI affine point -> 16 words
@@ -15,9 +18,10 @@
 #include <iostream>
 #include <sstream>
 #include <string>
+#include <vector>
 
 #include "hipemu.h"
-#include "curve29.cuh"
+#include "field29_calc.h"
 
 using namespace srs;
 
@@ -56,16 +60,16 @@ static void field_op(const std::string &op, std::istringstream &in) {
     else if (op == "redlazy") { f29_t a = rd9<P>(in); pr(G::reduce_lazy(a).v, 9); }
     else if (op == "unpack") { fe_t a = rd8(in); pr(G::unpack(a).v, 9); }
     else if (op == "pack") { f29_t a = rd9<P>(in); pr(G::pack(a).v, 8); }
+    else if (op == "mul8") { fe_t a = rd8(in), b = rd8(in); pr(Fp<P>::mul(a, b).v, 8); }
     else if (op == "sub" || op == "neg") {
         unsigned cp, e;
         in >> std::dec >> cp >> e;
         const bool neg = op == "neg";
         f29_t a = neg ? G::zero() : rd9<P>(in), b = rd9<P>(in);
-        bool ok = try_sub<P, 1, 0>(cp, e, neg, a, b) || try_sub<P, 2, 0>(cp, e, neg, a, b) || try_sub<P, 3, 0>(cp, e, neg, a, b) ||
-                  try_sub<P, 5, 1>(cp, e, neg, a, b) || try_sub<P, 6, 2>(cp, e, neg, a, b) || try_sub<P, 7, 2>(cp, e, neg, a, b) ||
-                  try_sub<P, 8, 0>(cp, e, neg, a, b) || try_sub<P, 10, 0>(cp, e, neg, a, b) || try_sub<P, 13, 0>(cp, e, neg, a, b) ||
-                  try_sub<P, 31, 0>(cp, e, neg, a, b) || try_sub<P, 3, 2>(cp, e, neg, a, b) || try_sub<P, 12, 2>(cp, e, neg, a, b) ||
-                  try_sub<P, 6, 0>(cp, e, neg, a, b) || try_sub<P, 8, 1>(cp, e, neg, a, b);
+        bool ok = false;
+#define SRS_CALC_TRY(CP, E) ok = ok || try_sub<P, CP, E>(cp, e, neg, a, b);
+        SRS_CALC_SUB_PAIRS(SRS_CALC_TRY)
+#undef SRS_CALC_TRY
         if (!ok) std::printf("unsupported\n");
     } else std::printf("unsupported\n");
 }
@@ -88,6 +92,33 @@ static void curve_op(const std::string &op, std::istringstream &in) {
             acc = op == "chain" ? E::madd(acc, E::load(q, neg != 0)) : E::madd_signed(acc, E::load_raw(q), neg != 0);
         }
         prp(E::pack(acc));
+    } else if (op == "chainf" || op == "chainf_raw") {
+        unsigned has_init, n;
+        in >> std::dec >> has_init;
+        xyzz_t init;
+        if (has_init) rdp(init);
+        in >> std::dec >> n;
+        std::vector<uint32_t> ent((size_t)n * CALC_ENTRY_WORDS);
+        for (unsigned i = 0; i < n; ++i) {
+            for (int j = 0; j < 16; ++j) { unsigned long long v; in >> std::hex >> v; ent[i * CALC_ENTRY_WORDS + j] = (uint32_t)v; }
+            unsigned neg;
+            in >> std::dec >> neg;
+            ent[i * CALC_ENTRY_WORDS + 16] = neg;
+        }
+        if (n == 0) { std::printf("unsupported\n"); return; }
+        bool exc;
+        const xyzz29_t acc = calc_chainf<C>(has_init ? &init : nullptr, n, ent.data(), exc);
+        uint32_t w[37];
+        if (op == "chainf") {
+            const xyzz_t o = E::pack(acc);
+            std::memcpy(w, &o, sizeof o);
+            w[32] = exc;
+            pr(w, 33);
+        } else {
+            std::memcpy(w, &acc, sizeof acc);
+            w[36] = exc;
+            pr(w, 37);
+        }
     } else if (op == "addp") {
         xyzz_t a, b;
         rdp(a); rdp(b);

@@ -70,6 +70,46 @@ def test_ntt_pass_structures(srs, oracle):
         _lib.lib().srs_ntt_set_max_radix_bits(8)
 
 
+def _extreme_inputs(O, k, seed):
+    """Canonical Montgomery words that drive the lazy tile to its bounds: p - 1 is the largest admissible bit pattern."""
+    from oracle import pyref as P
+    n = 1 << k
+    pm1 = np.array([[((P.MODULI[0] - 1) >> (64 * i)) & ((1 << 64) - 1) for i in range(4)]], dtype=np.uint64)
+    one = O.ints_to_mont(O.FR, [1])                        # the field's 1 (R mod p as a word)
+    zero = np.zeros((n, 4), np.uint64)
+    alt = _rand(O, n, seed)
+    alt[::2] = pm1
+    first, last, lead = zero.copy(), zero.copy(), zero.copy()
+    first[0], last[n - 1], lead[0] = one, one, pm1
+    return {"all p - 1": np.repeat(pm1, n, axis=0), "p - 1 / random": alt, "all zero": zero, "1 at 0": first, "1 at n - 1": last,
+            "(p - 1, 0, 0, ...)": lead}
+
+
+# max radix bits -> size, as in test_ntt_pass_structures: 2, 3 and 4 passes
+_SPLITS = {12: (4,), 16: (4,), 15: (5,), 17: (6,), 21: (7,)}
+
+
+@pytest.mark.parametrize("k", [8, 11, 12, 15, 16, 17, 20, 21])
+def test_ntt_lazy_tile_extremes(srs, oracle, k):
+    """The GPU twin of test_emu_ntt_lazy_tile_extremes: the real kernels on the inputs that push the lazy 9 x 29-bit tile to its limits -- every
+    element p - 1, alternating p - 1 / random, all zero, a single 1 at either end, (p - 1, 0, 0, ...) -- all four transforms, bit-exact
+    against the oracle; at the default radix and, at the sizes test_ntt_pass_structures uses for 2, 3 and 4 passes, with the digit width
+    limited to 4 .. 7 bits (each oracle result is computed once and serves both).  The words are canonical Montgomery words as everywhere
+    in this file: the tile derives its bounds from "canonical input" (csrc/ntt.hip), so p - 1 everywhere is the worst ADMISSIBLE input
+    and non-canonical words are outside the contract -- they are not fed."""
+    from sirius_amd import _lib
+    O = oracle
+    try:
+        for name, a in _extreme_inputs(O, k, 300 + k).items():
+            want = {fn: getattr(O, fn)(a) for fn in FNS}
+            for bits in (8,) + _SPLITS.get(k, ()):
+                assert _lib.lib().srs_ntt_set_max_radix_bits(bits) == bits
+                for fn in FNS:
+                    assert np.array_equal(getattr(srs.fft, fn)(a.copy()), want[fn]), (k, name, fn, bits)
+    finally:
+        _lib.lib().srs_ntt_set_max_radix_bits(8)
+
+
 def test_ntt_microbench_size_properties(srs, oracle):
     """BASELINE config 5 size (2^24), too slow for the oracle in a unit test: size-independent properties --
     round trip, linearity against a second vector, and a spot check of one output against the definition."""
