@@ -1,4 +1,5 @@
-// rowprog.h -- internal interface of the row-program engine (see rowprog.hip).
+// rowprog.h -- internal interface of the row-program engine (kernels and launch code: rowprog.hip; the host-only compiler
+// behind create(): rowprog_compile.hip).
 #pragma once
 #include <memory>
 #include <string>

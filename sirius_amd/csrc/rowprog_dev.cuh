@@ -101,7 +101,7 @@ __device__ __forceinline__ fe_t ld_adv(const RowCtx &C, uint32_t col, uint32_t r
     return r;
 }
 
-// sweep form (rowprog.hip, emit_sweep_source): an advice leaf as an affine function of the evaluation point,
+// sweep form (rowprog_compile.hip, emit_sweep_source): an advice leaf as an affine function of the evaluation point,
 // value(pt) = cur + pt * step.  Only for the point sets without a coefficient table (C.wcoef == nullptr):
 //   J == 1: the witness itself;  J == 2: W[0] + pt W[1] (cross terms);  J == 2, half: the Lagrange fold at integer points.
 template <class F>

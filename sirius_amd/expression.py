@@ -1,7 +1,7 @@
 """`Expression` -- host-side mirror of reference src/polynomial/expression.rs:112-120.
 
 Only construction and serialisation live here: compression, homogenisation and compilation to the
-device row program happen inside the library (csrc/rowprog.hip), as they do inside
+device row program happen inside the library (csrc/rowprog_compile.hip), as they do inside
 `PlonkStructure` in the reference.  Nodes are tuples:
   ('const', int) ('poly', index, rotation) ('chal', index) ('neg', a) ('sum', a, b) ('prod', a, b) ('scaled', a, int)
 """

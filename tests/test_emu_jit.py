@@ -120,6 +120,13 @@ def test_emu_jit_random_circuits(emu_jit, oracle):
     assert done == 8
 
 
+def test_emu_compiler_output_pinned(emu_jit):
+    """what the row-program compiler derives and emits for the recorded structures (tests/rowprog_cases.py): fingerprints, kernel ids,
+    length and SHA-256 of every emitted source, as recorded"""
+    import rowprog_cases
+    rowprog_cases.check(emu_jit)
+
+
 def test_emu_jit_lookup_structure(emu_jit, oracle):
     """a structure with lookup arguments: its lookup-extended cross-term program (multi-round witness columns) through the compiled kernel"""
     from lookup_cases import run_lookup_case

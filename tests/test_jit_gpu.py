@@ -52,3 +52,10 @@ def test_jit_lookup_structure(srs, oracle):
     """A structure with a vector lookup at 2^14 rows runs its (lookup-extended) cross-term program through hiprtc too."""
     from lookup_cases import run_lookup_case
     run_lookup_case(srs, oracle, "vector", 14)
+
+
+def test_compiler_output_pinned(srs):
+    """the compiler inside the real library emits what the CPU emulator build of it does: the recorded structures of
+    tests/rowprog_cases.py (2^3 rows each), every recorded field"""
+    import rowprog_cases
+    rowprog_cases.check(srs)

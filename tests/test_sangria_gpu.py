@@ -346,6 +346,14 @@ def test_fold_then_decider(srs, oracle):
     _fold_then_decide(srs, oracle, 1, 1, 6, (5,))       # secondary: grumpkin / Fq
 
 
+def _high_degree_gates(M, n_gates):
+    """n gates q_i * (a * b(rot) - c) over n fixed and 3 advice columns, in oracle.expr's (M.Poly) or sirius_amd.expression's spelling"""
+    nfix = n_gates
+    mk = lambda i: M.Prod(M.Poly(i), M.Sum(M.Prod(M.Poly(nfix), M.Poly(nfix + 1, 1 if i % 3 == 0 else 0)), M.Neg(M.Poly(nfix + 2)))) \
+        if hasattr(M, "Poly") else M.Product(M.Polynomial(i), M.Sum(M.Product(M.Polynomial(nfix), M.Polynomial(nfix + 1, 1 if i % 3 == 0 else 0)), M.Negated(M.Polynomial(nfix + 2))))
+    return [mk(i) for i in range(n_gates)]
+
+
 def _high_degree_case(S, O, field, k, n_gates):
     """Folding degree above 8 (n gates compressed with y^(n-1): degree = 2 + n - 1): the cross terms take several
     passes over the evaluation points, the error fold several launches.  Checked against the reference's symbolic
@@ -355,10 +363,8 @@ def _high_degree_case(S, O, field, k, n_gates):
     rows = 1 << k
     rng = np.random.default_rng(n_gates * 7 + k)
     nfix, nadv = n_gates, 3
-    mk = lambda M, i: M.Prod(M.Poly(i), M.Sum(M.Prod(M.Poly(nfix), M.Poly(nfix + 1, 1 if i % 3 == 0 else 0)), M.Neg(M.Poly(nfix + 2)))) \
-        if hasattr(M, "Poly") else M.Product(M.Polynomial(i), M.Sum(M.Product(M.Polynomial(nfix), M.Polynomial(nfix + 1, 1 if i % 3 == 0 else 0)), M.Negated(M.Polynomial(nfix + 2))))
-    og = [mk(OE, i) for i in range(n_gates)]
-    pg = [mk(X, i) for i in range(n_gates)]
+    og = _high_degree_gates(OE, n_gates)
+    pg = _high_degree_gates(X, n_gates)
     fixed = [rand_fe(rng, rows, 0.5) for _ in range(nfix)]
     W1, W2 = rand_fe(rng, nadv * rows), rand_fe(rng, nadv * rows)
     St = S.PlonkStructure(field, k, [], fixed, nadv, pg)
