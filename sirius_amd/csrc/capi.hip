@@ -1093,7 +1093,7 @@ int commit_streamed_core(StreamRes ck_, const std::vector<Seg> &segs, size_t n, 
     std::vector<bool> launched(chunks, false);
     // every chunk on the 16-bit windows: the chunks fold their buckets into one running set and only the last one is reduced
     bool fold = chunks > 1;
-    for (size_t j = 0; j < chunks; ++j) fold = fold && local(cut[j], cut[j + 1]) > 0 && msm::may_fold(ck->key, (uint32_t)local(cut[j], cut[j + 1]));
+    for (size_t j = 0; j < chunks; ++j) fold = fold && local(cut[j], cut[j + 1]) > 0;
     msm::reserve(ck->key, (uint32_t)per, 1);
     auto upload = [&](size_t j) {
         if (W == 1) {

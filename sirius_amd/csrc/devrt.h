@@ -71,9 +71,10 @@ struct Arena {
         cap = bytes;
     }
     void reset() { used = 0; }
+    static size_t pad(size_t bytes) { return (bytes + 255) & ~(size_t)255; }      // what a take of `bytes` uses
     template <class T>
     T *take(size_t count) {
-        size_t bytes = (count * sizeof(T) + 255) & ~(size_t)255;
+        size_t bytes = pad(count * sizeof(T));
         if (used + bytes > cap) {
             set_error("internal: arena overflow");
             throw DeviceError{5};
@@ -82,7 +83,6 @@ struct Arena {
         used += bytes;
         return p;
     }
-    static size_t pad(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
     void release() {
         if (base) (void)hipFree(base);
         base = nullptr;

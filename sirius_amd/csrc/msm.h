@@ -69,31 +69,32 @@ struct Key {
     bool compact_scalars = false;   // world > 1: the scalar vectors handed to run() hold ONLY this rank's stripes, gathered (multi-device keys)
     affine_t *table = nullptr;
     affine_t *table_w = nullptr;   // T_w[w][i] = 2^(20 w) P_i, w < NWIN_W (keys of >= 2^WIDE_MIN_KEY_LOG bases; owned by the key: release())
-    xyzz_t *fold_buckets = nullptr;   // running bucket sums of a chunked commit (enqueue(.., fold)); owned by the key
-    bool slot_wide[LANDING_SLOTS] = {};       // landing slot -> which pipeline produced it (finish() combines 3 or 4 partial sums)
-    // slot mode (see SLOT_LOG): owned by the key, grow-only
+    uint64_t stat_slot_sets = 0, stat_hot_sets = 0, stat_redo = 0, stat_other_sets = 0;   // srs_ck_msm_stats
+    uint64_t last_entries = 0;        // non-zero digits (= bucket additions) of the last commit that ran in slot mode (note_commit) ...
+    uint64_t last_scalars = 0;        // ... and its scalars (both set by note_commit, both 0 when the commit had no slot-mode set): the density the next streamed commit's chunk cuts are chosen for
+
+    // ---- run state: read and written by msm.hip only; everything here that points at memory is owned by the key (release()) ----
+    Arena arena;              // per-key scratch (grow-only)
+    void *h_result = nullptr; // page-locked landing buffer of the 3 partial sums per MSM (direct copy, no staging hop)
+    // what enqueue() left in a landing slot: the wide pipeline produced it (finish() combines 4 partial sums instead of 3); the set ran
+    // in slot mode, with its overflow kernels launched, and had this many MSMs (overflow_missed(), note_commit())
+    struct Landing { bool wide = false, slot_mode = false, ovf_on = false; uint32_t batch = 0; } landing[LANDING_SLOTS];
+    xyzz_t *fold_buckets = nullptr;   // running bucket sums of a chunked commit (enqueue(.., fold)) outside slot mode
+    // slot mode (see SLOT_LOG), grow-only
     xyzz_t *slots = nullptr;          // [batch][NBUCKET][S] persistent partial sums of the running commit
     size_t slots_pts = 0;
     uint8_t *used = nullptr;          // [2][BATCH_ARGS][NBUCKET]: slots of a bucket that hold a sum (parity = set index inside the commit)
     uint32_t *h_ovf = nullptr;        // page-locked [2][LANDING_SLOTS][BATCH_ARGS]: parts beyond the slots, then non-zero digits, reported by k_plan_s
-    uint64_t last_entries = 0;        // non-zero digits (= bucket additions) of the last commit that ran in slot mode (note_commit) ...
-    uint64_t last_scalars = 0;        // ... and its scalars (both set by note_commit, both 0 when the commit had no slot-mode set): the density the next streamed commit's chunk cuts are chosen for
     uint32_t slot_s = 0;              // S of the running commit
     uint32_t seq = 0;                 // sets enqueued in the running commit
     bool commit_ovf = false;          // the running commit launches the overflow kernels
     bool expect_ovf = expect_ovf_initial();   // prediction for the next commit: hot buckets seen in one of the last few commits (note_commit); a new key expects them
     uint32_t cold_streak = 0;         // commits in a row without hot buckets while they were expected
-    bool slot_mode[LANDING_SLOTS] = {};     // landing slot -> the set ran in slot mode ...
-    bool slot_ovf_on[LANDING_SLOTS] = {};   // ... with its overflow kernels launched
-    uint32_t slot_batch[LANDING_SLOTS] = {};
-    uint64_t stat_slot_sets = 0, stat_hot_sets = 0, stat_redo = 0, stat_other_sets = 0;   // srs_ck_msm_stats
-    Arena arena;              // per-key scratch (grow-only)
-    void *h_result = nullptr; // page-locked landing buffer of the 3 partial sums per MSM (direct copy, no staging hop)
 };
 
 // fills table[len .. 16*len) from table[0 .. len); keys that want it (wants_wide_table) also get table_w
 void build_table(Key &k, hipStream_t stream);
-// frees what the key owns besides `table`: table_w, the scratch arena, the landing buffer
+// frees what the key owns besides `table`: table_w and the run state
 void release(Key &k);
 // fills table[0 .. len) with the synthetic key (see k_gen_bases)
 void generate_bases(Key &k, uint64_t seed, hipStream_t stream);
@@ -120,9 +121,8 @@ void run(Key &k, const fe_t *const *scalars_dev, const uint32_t *n_host, uint32_
 // `fold`: the sets of a chunked commit share ONE bucket set (the buckets are the digit values, whatever the base offset), and the
 // bucket reduction is linear: a set with FOLD_FIRST / FOLD_MIDDLE only adds its bucket sums into the key's running buckets (no
 // reduction, no result), the FOLD_LAST set adds its own and reduces the total -- one k_rowcol + k_reduce_final + host finish per commit
-// instead of one per chunk.  batch == 1, 16-bit-window sets only (may_fold()).
+// instead of one per chunk.  batch == 1, 16-bit-window sets only (a chunked commit never takes the wide windows).
 enum Fold { FOLD_NONE = 0, FOLD_FIRST = 1, FOLD_MIDDLE = 2, FOLD_LAST = 3 };
-bool may_fold(const Key &k, uint32_t n);     // always true since r04 (the sets of a chunked commit never take the wide-window pipeline)
 bool enqueue(Key &k, const fe_t *const *scalars_dev, const uint32_t *n_host, const uint32_t *base_host, uint32_t batch, int is_mont,
              hipStream_t stream, uint32_t slot, Fold fold = FOLD_NONE);
 void finish(Key &k, uint32_t batch, uint32_t slot, bool launched, xyzz_t *result_host);

@@ -31,6 +31,9 @@
 // set (k_plan_s) picks the part length on the device; parts beyond the slots (hot buckets) go through the level kernels into the
 // bucket's last slot, launched only when the key expects them (msm.h: overflow_missed / note_commit).  Whole MSMs of >= 2^23 scalars
 // take the 13 x 20-bit "wide" windows over a second table (16 virtual MSMs of 2^15 buckets each).
+// Host driver (end of this file): enqueue() picks one of three flows (enqueue_t: levels, enqueue_slots_t: slot mode, enqueue_wide_t).  Each
+// computes its shape once (*_shape: sizes, grids and every tunable), carves the key's arena by its one buffer list (*_layout, also the
+// sizer behind reserve()) and runs the shared stages: sort_front, accum_levels, reduce_buckets, land.
 // The 29-bit products of THIS translation unit chain every column's multiply-accumulates from the previous column's carry (inline
 // v_mad_u64_u32, field29.cuh): no 64-bit join per column, 127 instead of 132 VGPRs in k_accum0 / k_accum0s (4 waves per SIMD instead of
 // 3): 13.85 -> 14.4 G mixed additions/s, profiles/r04_ab_slots_cuts.txt; one asm statement per RUN of multiply-accumulates, not per
@@ -44,6 +47,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <numeric>
 #include <vector>
 
 namespace srs {
@@ -1672,7 +1676,7 @@ __global__ void SRS_KERNEL_BOUNDS(256, 1)
 }
 
 // ---------------------------------------------------------------------------------------------
-// host orchestration
+// key expansion and table upkeep (host side)
 // ---------------------------------------------------------------------------------------------
 static inline uint32_t ceil_div(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
 
@@ -1770,8 +1774,8 @@ void build_table(Key &k, hipStream_t stream) {
     if (k.curve == 0) build_table_t<Bn256>(k, stream); else build_table_t<Grumpkin>(k, stream);
 }
 
-// number of thread-sequential levels after level 0 so that the wavefront-level final pass sees
-// at most ~FINAL_FANIN parts per bucket even if every entry fell into one bucket
+// ---- host driver: three flows (16-bit windows with levels / in slot mode, wide windows) over shared stages -----------------------
+
 // gathered mixed additions per level-0 thread.  Two losses pull in opposite directions: every part leaves a partial sum the
 // later levels combine with the dearer full additions (+ 1.4 / L0 of the level-0 work), and the launch ends with a
 // partly filled last wave of workgroups (the chip holds 2^18 level-0 threads at a time: + ~0.5 / waves, waves = entries /
@@ -1799,9 +1803,9 @@ static uint32_t acc1_quad_max() {
     return (lg >= 1 && lg <= 24) ? (1u << lg) : ACC1_QUAD_MAX;
 }
 
-static int levels_for(uint64_t max_entries) {
-    const uint64_t ACC_L0 = 1ull << l0_log_for(max_entries);
-    uint64_t parts = (max_entries + ACC_L0 - 1) / ACC_L0;
+// number of thread-sequential levels, level 0 included, so that the wavefront-level final pass sees at most ~FINAL_FANIN parts
+// per bucket even if every entry fell into one bucket (`parts`: the level-0 parts of that bucket)
+static int levels_for(uint64_t parts) {
     int levels = 1;
     while (parts > FINAL_FANIN && levels < MAX_LEVELS) {
         parts = (parts + ACC_L1 - 1) / ACC_L1;
@@ -1818,63 +1822,206 @@ static bool use_two_pass(uint64_t M, uint32_t batch) {
     return M * batch >= TWO_PASS_MIN_SLOTS;
 }
 
-size_t workspace_bytes(uint32_t n_max, uint32_t batch) {
-    uint64_t M = (uint64_t)n_max * NWIN;
-    int levels = levels_for(M);
-    size_t plan_stride = (size_t)(levels + 1) * (NBUCKET + 1) + 4;
-    uint64_t parts0 = (M >> l0_log_for(M)) + NBUCKET + 1;
-    uint64_t parts1 = parts0 / ACC_L1 + NBUCKET + 1;
-    size_t per = 0;
-    per += Arena::pad(M * sizeof(uint16_t));                 // digits
-    per += Arena::pad(M * sizeof(uint32_t));                 // sorted
-    per += 2 * Arena::pad(NBUCKET * sizeof(uint32_t));       // count, cursor
-    per += Arena::pad(plan_stride * sizeof(uint32_t));
-    per += Arena::pad(parts0 * sizeof(xyzz_t));              // ping
-    per += Arena::pad(parts0 * sizeof(uint16_t));            // thread -> bucket map of level 0
-    per += Arena::pad(parts1 * sizeof(xyzz_t));              // pong
-    per += Arena::pad((size_t)NBUCKET * sizeof(xyzz_t));     // buckets
-    per += Arena::pad((RED_ROWS + RED_COLS) * sizeof(xyzz_t));
-    if (use_two_pass(M, batch)) {
-        per += Arena::pad(M * sizeof(uint16_t)) + Arena::pad(M * sizeof(uint32_t));                     // grouped keys / payloads
-        per += Arena::pad((size_t)SEG * (SORT_TARGET_BLOCKS + 2 * NWIN) * sizeof(uint32_t));            // per-tile segment counts
-    }
-    return per * batch + Arena::pad(3 * batch * sizeof(xyzz_t)) + 4096;
+static uint32_t slot_log() {
+    const int64_t lg = tuning::get_or(tuning::MSM_SLOT_LOG, 0);
+    return (lg >= 2 && lg <= 8) ? (uint32_t)lg : SLOT_LOG;
+}
+// the part length a large set prefers when its buckets would fit shorter parts: 2^4
+static uint32_t slot_want_cap() { return 4u; }
+
+// ---- shapes: what the sizes, grids and kernel arguments of a set of launches follow from.  Every tunable-dependent choice is read
+// ONCE per workspace_bytes* / enqueue call, into the shape; everything downstream takes it from there. ---------------------------------
+struct LevelShape {            // every flow
+    uint64_t M;                // digit slots = entry capacity (per MSM of a batch)
+    int levels;                // accumulation levels incl. level 0 (slot mode: of the parts beyond the slots)
+    size_t plan_stride;        // plan words per MSM / segment
+    uint64_t cap0, cap1;       // points in ping = level-0 threads (= parts, worst case) and in pong = parts after level 1 (per MSM of a batch)
+    uint32_t quad_max;         // acc1_quad_max()
+};
+struct SetShape : LevelShape { // the two flows of the 16-bit windows: + their counting sort
+    bool two_pass;
+    uint32_t tile, tiles;      // scalars per workgroup of k_hist / k_group / k_scatter, workgroups per window
+};
+struct NarrowShape : SetShape { uint32_t l0_log; };         // log2 of the part length (slot mode chooses it on the device: k_plan_s)
+struct SlotShape : SetShape { uint32_t S, nred; };          // slots per bucket; reduction levels at the end of a commit (8 inputs per output)
+struct WideShape : LevelShape { uint32_t l0_log, T, tiles_g; };   // log2 of the part length; workgroups of the segment passes, of the sort inside the segments
+
+static void sort_shape(SetShape &h, uint32_t n_max, uint32_t batch) {
+    h.M = (uint64_t)n_max * NWIN;
+    h.quad_max = acc1_quad_max();
+    h.two_pass = use_two_pass(h.M, batch);
+    // tile = digits per workgroup: large enough that the fixed 2^15-bin zero/scan of the LDS histogram is
+    // amortised, small enough to give ~SORT_TARGET_BLOCKS workgroups (one per CU, 128 KiB LDS each)
+    h.tile = (uint32_t)((h.M * batch + SORT_TARGET_BLOCKS - 1) / SORT_TARGET_BLOCKS);
+    h.tile = (h.tile + 1023u) & ~1023u;
+    if (h.tile < SORT_TILE_MIN) h.tile = SORT_TILE_MIN;
+    h.tiles = ceil_div(n_max, h.tile);
+}
+static NarrowShape narrow_shape(uint32_t n_max, uint32_t batch) {
+    NarrowShape h;
+    sort_shape(h, n_max, batch);
+    h.l0_log = l0_log_for(h.M);
+    h.levels = levels_for((h.M + (1ull << h.l0_log) - 1) >> h.l0_log);
+    h.plan_stride = (size_t)(h.levels + 1) * (NBUCKET + 1) + 4;
+    h.cap0 = (h.M >> h.l0_log) + NBUCKET + 1;
+    h.cap1 = h.cap0 / ACC_L1 + NBUCKET + 1;
+    return h;
+}
+static SlotShape slot_shape(uint32_t n_max, uint32_t batch) {
+    SlotShape h;
+    sort_shape(h, n_max, batch);
+    const uint32_t lg = slot_log();
+    h.S = 1u << lg;
+    h.nred = (lg + 2) / 3;
+    // parts = sum_b ceil(c_b / L0) <= E / L0 + NBUCKET, and k_plan_s picks L0 >= (mean load) / (S - 1): never more than NBUCKET * S parts;
+    // L0 >= 2^SLOT_L0_MIN_LOG bounds them for small sets
+    h.cap0 = std::min<uint64_t>((uint64_t)NBUCKET * h.S, (h.M >> SLOT_L0_MIN_LOG) + NBUCKET);
+    h.cap1 = h.cap0 / ACC_L1 + NBUCKET + 1;
+    h.levels = levels_for(h.cap0);
+    h.plan_stride = (size_t)(h.levels + 2) * (NBUCKET + 1) + 4;
+    return h;
+}
+static WideShape wide_shape(uint32_t n) {
+    WideShape w;
+    w.M = (uint64_t)n * NWIN_W;
+    w.quad_max = acc1_quad_max();
+    w.l0_log = l0_log_for(w.M);
+    w.levels = levels_for((w.M + (1ull << w.l0_log) - 1) >> w.l0_log);      // worst case: every entry in one bucket of one segment
+    w.plan_stride = (size_t)(w.levels + 1) * (NBUCKET + 1) + 4;
+    w.cap0 = (w.M >> w.l0_log) + (uint64_t)NSEG_W * (NBUCKET + 1);
+    w.cap1 = w.cap0 / ACC_L1 + (uint64_t)NSEG_W * (NBUCKET + 1);
+    w.T = ceil_div(n, WIDE_TILE);
+    w.tiles_g = SORT_TARGET_BLOCKS;                          // the tile size is chosen on the device (k_seg_scan) so that this many suffice
+    return w;
 }
 
-// launches one set of <= BATCH_ARGS MSMs on `stream`; the 3 partial sums of MSM m land in landing slot `slot`
-// (page-locked host memory) in stream order.  Returns false when every MSM is empty (nothing was launched).
-template <class C>
-static bool enqueue_t(Key &k, const fe_t *const *scalars_dev, const uint32_t *n_host, const uint32_t *base_host, uint32_t batch,
-                      int is_mont, hipStream_t stream, uint32_t slot, Fold fold) {
-    uint32_t n_max = 0;
-    for (uint32_t m = 0; m < batch; ++m) n_max = std::max(n_max, n_host[m]);
-    if (n_max == 0) return false;
-    const uint64_t M = (uint64_t)n_max * NWIN;
-    const int levels = levels_for(M);
-    const uint32_t l0_log = l0_log_for(M);
-    const size_t plan_stride = (size_t)(levels + 1) * (NBUCKET + 1) + 4;
-    const uint64_t parts0_cap = (M >> l0_log) + NBUCKET + 1;
-    const uint64_t parts1_cap = parts0_cap / ACC_L1 + NBUCKET + 1;
-
-    Arena &A = k.arena;
-    A.reserve(workspace_bytes(n_max, batch));
+// ---- workspace: every flow lists its buffers ONCE, as a walk over a "walker" -- the Sizer, which adds up what the arena would hand out
+// (workspace_bytes*, so reserve()), or the Arena, which hands it out (enqueue).  reserve() must be right for a LATER enqueue (growing the
+// arena mid-commit would free memory still in use): one list per flow cannot disagree with itself, and carve() checks it. ---------------
+struct Sizer {
+    size_t used = 0;
+    template <class T>
+    T *take(size_t count) {
+        used += Arena::pad(count * sizeof(T));
+        return nullptr;
+    }
+};
+template <class Walk>
+static size_t sized(Walk walk) {
+    Sizer s;
+    walk(s);
+    return s.used;
+}
+template <class Walk>
+static auto carve(Arena &A, Walk walk) {
+    const size_t need = sized(walk);
+    A.reserve(need);
     A.reset();
-    xyzz_t *d_out = A.take<xyzz_t>(3 * (size_t)batch);
-    uint16_t *dig = A.take<uint16_t>(M * batch);
-    uint32_t *sorted = A.take<uint32_t>(M * batch);
-    uint32_t *count = A.take<uint32_t>((size_t)NBUCKET * batch);
-    uint32_t *cursor = A.take<uint32_t>((size_t)NBUCKET * batch);
-    uint32_t *plan = A.take<uint32_t>(plan_stride * batch);
-    xyzz_t *ping = A.take<xyzz_t>(parts0_cap * batch);
-    uint16_t *tb = A.take<uint16_t>(parts0_cap * batch);
-    xyzz_t *pong = A.take<xyzz_t>(parts1_cap * batch);
-    xyzz_t *buckets = A.take<xyzz_t>((size_t)NBUCKET * batch);
-    xyzz_t *rc = A.take<xyzz_t>((size_t)(RED_ROWS + RED_COLS) * batch);
-    const bool two_pass = use_two_pass(M, batch);
-    uint16_t *gkey = two_pass ? A.take<uint16_t>(M * batch) : nullptr;
-    uint32_t *gpay = two_pass ? A.take<uint32_t>(M * batch) : nullptr;
-    uint32_t *tile_hist = two_pass ? A.take<uint32_t>((size_t)SEG * (SORT_TARGET_BLOCKS + 2 * NWIN) * batch) : nullptr;
+    const auto bufs = walk(A);
+    if (A.used != need) {
+        set_error("internal: msm workspace: the arena walk and the sizer disagree");
+        throw DeviceError{5};
+    }
+    return bufs;
+}
 
+struct SetBufs {               // what both flows of the 16-bit windows carve, each x batch
+    xyzz_t *d_out, *ping, *pong, *rc;              // the 3 partial sums per MSM; partial sums of the levels; row / column sums
+    uint16_t *dig, *tb;                            // digits; thread -> bucket map of level 0
+    uint32_t *sorted, *count, *cursor, *plan;
+    uint16_t *gkey;                                // two-pass scatter only: grouped keys / payloads, per-tile segment counts
+    uint32_t *gpay, *tile_hist;
+};
+struct NarrowBufs : SetBufs { xyzz_t *buckets; };
+struct SlotBufs : SetBufs { xyzz_t *red_a, *red_b; };       // ping / pong of the slot reduction
+// head and tail of both lists: sort_front() reads either flow through SetBufs, so the common buffers are taken in one place
+template <class W>
+static void take_set_head(W &A, const SetShape &h, uint32_t batch, SetBufs &b) {
+    b.d_out = A.template take<xyzz_t>(3 * (size_t)batch);
+    b.dig = A.template take<uint16_t>(h.M * batch);
+    b.sorted = A.template take<uint32_t>(h.M * batch);
+    b.count = A.template take<uint32_t>((size_t)NBUCKET * batch);
+    b.cursor = A.template take<uint32_t>((size_t)NBUCKET * batch);
+    b.plan = A.template take<uint32_t>(h.plan_stride * batch);
+    b.ping = A.template take<xyzz_t>(h.cap0 * batch);                      // slot mode: the parts beyond the slots
+    b.tb = A.template take<uint16_t>(h.cap0 * batch);
+    b.pong = A.template take<xyzz_t>(h.cap1 * batch);
+}
+template <class W>
+static void take_set_tail(W &A, const SetShape &h, uint32_t batch, SetBufs &b) {
+    b.rc = A.template take<xyzz_t>((size_t)(RED_ROWS + RED_COLS) * batch);
+    b.gkey = h.two_pass ? A.template take<uint16_t>(h.M * batch) : nullptr;
+    b.gpay = h.two_pass ? A.template take<uint32_t>(h.M * batch) : nullptr;
+    b.tile_hist = h.two_pass ? A.template take<uint32_t>((size_t)SEG * (SORT_TARGET_BLOCKS + 2 * NWIN) * batch) : nullptr;
+}
+template <class W>
+static NarrowBufs narrow_layout(W &A, const NarrowShape &h, uint32_t batch) {
+    NarrowBufs b;
+    take_set_head(A, h, batch, b);
+    b.buckets = A.template take<xyzz_t>((size_t)NBUCKET * batch);
+    take_set_tail(A, h, batch, b);
+    return b;
+}
+template <class W>
+static SlotBufs slot_layout(W &A, const SlotShape &h, uint32_t batch) {
+    SlotBufs b;
+    take_set_head(A, h, batch, b);
+    b.red_a = A.template take<xyzz_t>((size_t)NBUCKET * (h.S / 8 + 1) * batch);
+    b.red_b = A.template take<xyzz_t>((size_t)NBUCKET * (h.S / 64 + 1) * batch);
+    take_set_tail(A, h, batch, b);
+    return b;
+}
+struct WideBufs {
+    xyzz_t *d_out, *d_seg, *ping, *pong, *buckets, *rc;     // the MSM's 4 sums; 4 per segment; as in SetBufs, for the 16 segments together
+    uint16_t *gkey, *gkey2, *tb;                   // grouped by segment (MSD pass), and again by sub-segment: the counting sort inside the
+    uint32_t *gpay, *gpay2, *tile_cnt, *tile_hist; // segments in two passes through LDS (k_group_g + k_scatter2_g); their per-tile counts
+    uint32_t *seg3;                                // seg_total, seg_off, tile_base, tile_base2: NSEG_W + 2 words each
+    uint32_t *sorted, *count, *cursor, *plan;
+    Link *link;
+};
+template <class W>
+static WideBufs wide_layout(W &A, const WideShape &w) {
+    WideBufs b;
+    b.d_out = A.template take<xyzz_t>(4);
+    b.d_seg = A.template take<xyzz_t>(4 * NSEG_W);
+    b.gkey = A.template take<uint16_t>(w.M);
+    b.gpay = A.template take<uint32_t>(w.M);
+    b.sorted = A.template take<uint32_t>(w.M);
+    b.tile_cnt = A.template take<uint32_t>((size_t)NSEG_W * w.T);
+    b.gkey2 = A.template take<uint16_t>(w.M);
+    b.gpay2 = A.template take<uint32_t>(w.M);
+    b.tile_hist = A.template take<uint32_t>((size_t)SEG * w.tiles_g);
+    b.seg3 = A.template take<uint32_t>(4 * (NSEG_W + 2));
+    b.link = A.template take<Link>(1);
+    b.count = A.template take<uint32_t>((size_t)NSEG_W * NBUCKET);
+    b.cursor = A.template take<uint32_t>((size_t)NSEG_W * NBUCKET);
+    b.plan = A.template take<uint32_t>(w.plan_stride * NSEG_W);
+    b.ping = A.template take<xyzz_t>(w.cap0);
+    b.tb = A.template take<uint16_t>(w.cap0);
+    b.pong = A.template take<xyzz_t>(w.cap1);
+    b.buckets = A.template take<xyzz_t>((size_t)NSEG_W * NBUCKET);
+    b.rc = A.template take<xyzz_t>((size_t)NSEG_W * (RED_ROWS + RED_COLS));
+    return b;
+}
+
+size_t workspace_bytes(uint32_t n_max, uint32_t batch) {
+    return sized([&](auto &A) { return narrow_layout(A, narrow_shape(n_max, batch), batch); });
+}
+static size_t workspace_bytes_slots(uint32_t n_max, uint32_t batch) {
+    return sized([&](auto &A) { return slot_layout(A, slot_shape(n_max, batch), batch); });
+}
+static size_t workspace_bytes_wide(uint32_t n) {
+    return sized([&](auto &A) { return wide_layout(A, wide_shape(n)); });
+}
+
+// ---- shared stages --------------------------------------------------------------------------------------------------------------
+// Sort front end of the 16-bit windows: scalars -> digits -> histogram -> the flow's plan (`launch_plan`: k_plan / k_plan_s) -> the
+// (bucket, table-index) pairs sorted by bucket, in one pass or two, and the thread -> bucket map of plan array `arr` in b.tb.
+// `group_maps`: the two-pass sort's k_group writes that map as well (k_expand's work), so that k_expand runs only after the single pass.
+template <class C, class LaunchPlan>
+static void sort_front(const Key &k, const SetShape &h, const SetBufs &b, const fe_t *const *scalars_dev, const uint32_t *n_host,
+                       const uint32_t *base_host, uint32_t batch, uint32_t n_max, int is_mont, hipStream_t stream, LaunchPlan launch_plan,
+                       bool group_maps, uint32_t arr) {
     BatchDesc bd;
     for (uint32_t m = 0; m < BATCH_ARGS; ++m) {
         bd.ptr[m] = m < batch ? scalars_dev[m] : nullptr;
@@ -1882,86 +2029,112 @@ static bool enqueue_t(Key &k, const fe_t *const *scalars_dev, const uint32_t *n_
         bd.base[m] = (m < batch && base_host) ? base_host[m] : 0;
     }
     const uint32_t s_rank = k.compact_scalars ? 0u : k.rank, s_world = k.compact_scalars ? 1u : k.world;
-    // tile = digits per workgroup: large enough that the fixed 2^15-bin zero/scan of the LDS histogram is
-    // amortised, small enough to give ~SORT_TARGET_BLOCKS workgroups (one per CU, 128 KiB LDS each)
-    uint32_t tile = (uint32_t)(((uint64_t)n_max * NWIN * batch + SORT_TARGET_BLOCKS - 1) / SORT_TARGET_BLOCKS);
-    tile = (tile + 1023u) & ~1023u;
-    if (tile < SORT_TILE_MIN) tile = SORT_TILE_MIN;
-    const uint32_t tiles = ceil_div(n_max, tile);
-    const Link *no_link = nullptr;
-    SRS_LAUNCH((k_digits<C>), (ceil_div(n_max, 256), batch), (256), 0, stream, bd, dig, (size_t)M, is_mont, s_rank, s_world, count,
+    const size_t M = (size_t)h.M;
+    SRS_LAUNCH((k_digits<C>), (ceil_div(n_max, 256), batch), (256), 0, stream, bd, b.dig, M, is_mont, s_rank, s_world, b.count,
                (uint32_t)(NBUCKET * batch));
-    SRS_LAUNCH(k_hist, (tiles, NWIN, batch), (SORT_THREADS), 0, stream, (const uint16_t *)dig, (size_t)M,
-               bd, count, tile, two_pass ? tile_hist : (uint32_t *)nullptr);
-    SRS_LAUNCH(k_plan, (batch, levels + 1), (PLAN_THREADS), 0, stream, (const uint32_t *)count, cursor, plan, plan_stride,
-               levels, l0_log, (uint32_t)ACC_L1_LOG, (const uint32_t *)nullptr);
-    if (two_pass) {
-        const uint32_t T1 = tiles * NWIN;
-        SRS_LAUNCH(k_scan_seg, (SEG, batch), (1024), 0, stream, tile_hist, T1, (const uint32_t *)plan, plan_stride);
-        SRS_LAUNCH(k_group, (tiles, NWIN, batch), (SORT_THREADS), 0, stream, (const uint16_t *)dig, (size_t)M, bd,
-                   (const uint32_t *)tile_hist, gkey, gpay, (size_t)M, (uint32_t)k.len, tile, (const uint32_t *)nullptr, (size_t)0,
-                   (uint16_t *)nullptr, (size_t)0, 0u);
+    SRS_LAUNCH(k_hist, (h.tiles, NWIN, batch), (SORT_THREADS), 0, stream, (const uint16_t *)b.dig, M, bd, b.count, h.tile, b.tile_hist);
+    launch_plan();
+    if (h.two_pass) {
+        const uint32_t T1 = h.tiles * NWIN;
+        SRS_LAUNCH(k_scan_seg, (SEG, batch), (1024), 0, stream, b.tile_hist, T1, (const uint32_t *)b.plan, h.plan_stride);
+        SRS_LAUNCH(k_group, (h.tiles, NWIN, batch), (SORT_THREADS), 0, stream, (const uint16_t *)b.dig, M, bd, (const uint32_t *)b.tile_hist,
+                   b.gkey, b.gpay, M, (uint32_t)k.len, h.tile, group_maps ? (const uint32_t *)b.plan : nullptr,
+                   group_maps ? h.plan_stride : (size_t)0, group_maps ? b.tb : nullptr, group_maps ? (size_t)h.cap0 : (size_t)0,
+                   group_maps ? arr : 0u);
         // 8 x ceil(tiles / 8) workgroups: the XCD-aware mapping of k_scatter2 needs every (XCD, slot) pair to exist
-        SRS_LAUNCH(k_scatter2, (8 * ceil_div(ceil_div(M, SORT_TILE2), 8), batch), (SORT_THREADS), 0, stream, (const uint16_t *)gkey,
-                   (const uint32_t *)gpay, (size_t)M, (const uint32_t *)plan, plan_stride, cursor, sorted, (size_t)M,
-                   (uint32_t)SORT_TILE2);
+        SRS_LAUNCH(k_scatter2, (8 * ceil_div(ceil_div(M, SORT_TILE2), 8), batch), (SORT_THREADS), 0, stream, (const uint16_t *)b.gkey,
+                   (const uint32_t *)b.gpay, M, (const uint32_t *)b.plan, h.plan_stride, b.cursor, b.sorted, M, (uint32_t)SORT_TILE2);
     } else {
-        SRS_LAUNCH(k_scatter, (tiles, NWIN, batch), (SORT_THREADS), 0, stream, (const uint16_t *)dig, (size_t)M,
-                   bd, cursor, sorted, (size_t)M, (uint32_t)k.len, tile);
+        SRS_LAUNCH(k_scatter, (h.tiles, NWIN, batch), (SORT_THREADS), 0, stream, (const uint16_t *)b.dig, M, bd, b.cursor, b.sorted, M,
+                   (uint32_t)k.len, h.tile);
     }
-    SRS_LAUNCH(k_expand, (NBUCKET / 4, batch), (256), 0, stream, (const uint32_t *)plan, plan_stride, tb, (size_t)parts0_cap, no_link, 1u);
+    if (!(h.two_pass && group_maps))
+        SRS_LAUNCH(k_expand, (NBUCKET / 4, batch), (256), 0, stream, (const uint32_t *)b.plan, h.plan_stride, b.tb, (size_t)h.cap0,
+                   (const Link *)nullptr, arr);
+}
 
-    uint64_t units = 0;
-    for (uint32_t m = 0; m < batch; ++m) units += n_host[m];
-    SRS_LAUNCH_TIMED("msm_accum0", units, (k_accum0<C>), (ceil_div(parts0_cap, ACC_THREADS), batch), (ACC_THREADS), 0, stream,
-                     (const uint32_t *)sorted, (size_t)M, (const uint32_t *)plan, plan_stride, (const uint16_t *)tb, (size_t)parts0_cap,
-                     (const affine_t *)k.table, ping, (size_t)parts0_cap, 1u << l0_log, no_link);
-    xyzz_t *cur = ping, *nxt = pong;
-    size_t cur_stride = parts0_cap, nxt_stride = parts1_cap;
-    uint64_t cap = parts0_cap;
-    for (int level = 1; level < levels; ++level) {
-        cap = cap / ACC_L1 + NBUCKET + 1;
-        SRS_LAUNCH((k_accum1<C>), (ceil_div(std::max<uint64_t>(cap, 4 * std::min<uint64_t>(cap, acc1_quad_max())), ACC_THREADS), batch), (ACC_THREADS), 0, stream,
-                   (const xyzz_t *)cur, cur_stride, (const uint32_t *)plan, plan_stride, level, nxt, nxt_stride,
-                   (uint32_t)ACC_L1, no_link, acc1_quad_max());
+// what the level kernels and the bucket reduction read of a set: its plan and the partial sums of the levels, ping (even levels) and
+// pong, with their strides per MSM of the batch -- 0 with a link: the segments of the wide flow share the buffers
+struct Parts {
+    const uint32_t *plan; size_t plan_stride;
+    xyzz_t *ping; size_t stride0;
+    xyzz_t *pong; size_t stride1;
+    const Link *link;
+};
+
+// accumulation levels 1 .. levels - 1 over ping / pong; `cap_inc`: what a level's worst-case part count adds to an eighth of the previous one
+template <class C>
+static void accum_levels(const Parts &p, const LevelShape &h, uint64_t cap_inc, uint32_t batch, hipStream_t stream) {
+    xyzz_t *cur = p.ping, *nxt = p.pong;
+    size_t cur_stride = p.stride0, nxt_stride = p.stride1;
+    uint64_t cap = h.cap0;
+    for (int level = 1; level < h.levels; ++level) {
+        cap = cap / ACC_L1 + cap_inc;
+        SRS_LAUNCH((k_accum1<C>), (ceil_div(std::max<uint64_t>(cap, 4 * std::min<uint64_t>(cap, h.quad_max)), ACC_THREADS), batch),
+                   (ACC_THREADS), 0, stream, (const xyzz_t *)cur, cur_stride, p.plan, h.plan_stride, level, nxt, nxt_stride, (uint32_t)ACC_L1,
+                   p.link, h.quad_max);
         std::swap(cur, nxt);
         std::swap(cur_stride, nxt_stride);
         // both buffers can hold any later level: parts shrink monotonically and pong >= level-1 cap
     }
-    (void)cur;
-    (void)cur_stride;
-    SRS_LAUNCH((k_accum_final<C>), (NBUCKET / (FINAL_THREADS / 64), batch), (FINAL_THREADS), 0, stream,
-               (const xyzz_t *)ping, (size_t)parts0_cap, (const xyzz_t *)pong, (size_t)parts1_cap,
-               (const uint32_t *)plan, plan_stride, buckets, no_link);
-    const xyzz_t *red_from = buckets;
+}
+
+// bucket reduction of `nmsm` MSMs / segments: row and column sums (k_rowcol: of `from`, or with from_buckets == 0 of `from` plus what
+// the plan left in ping / pong), then their `sums` weighted totals per MSM into d_sums
+template <class C>
+static void reduce_buckets(const Parts &p, uint32_t nmsm, const xyzz_t *from, int from_buckets, xyzz_t *rc, uint32_t sums, xyzz_t *d_sums,
+                           hipStream_t stream) {
+    SRS_LAUNCH((k_rowcol<C>), (RED_ROWS / 2 + RED_COLS, nmsm), (128), 0, stream, from, (const xyzz_t *)p.ping, p.stride0,
+               (const xyzz_t *)p.pong, p.stride1, p.plan, p.plan_stride, rc, p.link, from_buckets);
+    SRS_LAUNCH((k_reduce_final<C>), (sums, nmsm), (RED_THREADS), 0, stream, (const xyzz_t *)rc, d_sums);
+}
+
+// a set's `n` partial sums into landing slot `slot` (page-locked host memory), in stream order
+static void land(Key &k, const xyzz_t *d_out, size_t n, uint32_t slot, hipStream_t stream) {
+    if (!k.h_result) SRS_HIP_CHECK(hipHostMalloc(&k.h_result, 3 * (size_t)BATCH_ARGS * LANDING_SLOTS * sizeof(xyzz_t)));
+    xyzz_t *dst = static_cast<xyzz_t *>(k.h_result) + 3 * (size_t)BATCH_ARGS * slot;
+    SRS_HIP_CHECK(hipMemcpyAsync(dst, d_out, n * sizeof(xyzz_t), hipMemcpyDeviceToHost, stream));
+}
+
+// ---- the level flow of the 16-bit windows ---------------------------------------------------------------------------------------
+// launches one set of <= BATCH_ARGS MSMs on `stream`; the 3 partial sums of MSM m land in landing slot `slot`
+// (page-locked host memory) in stream order.  Returns false when every MSM is empty (nothing was launched).
+template <class C>
+static bool enqueue_t(Key &k, const fe_t *const *scalars_dev, const uint32_t *n_host, const uint32_t *base_host, uint32_t batch,
+                      uint32_t n_max, int is_mont, hipStream_t stream, uint32_t slot, Fold fold) {
+    if (n_max == 0) return false;
+    const NarrowShape h = narrow_shape(n_max, batch);
+    const NarrowBufs b = carve(k.arena, [&](auto &A) { return narrow_layout(A, h, batch); });
+    sort_front<C>(k, h, b, scalars_dev, n_host, base_host, batch, n_max, is_mont, stream, [&] {
+        SRS_LAUNCH(k_plan, (batch, h.levels + 1), (PLAN_THREADS), 0, stream, (const uint32_t *)b.count, b.cursor, b.plan, h.plan_stride,
+                   h.levels, h.l0_log, (uint32_t)ACC_L1_LOG, (const uint32_t *)nullptr);
+    }, false, 1u);
+    const Parts p{b.plan, h.plan_stride, b.ping, (size_t)h.cap0, b.pong, (size_t)h.cap1, nullptr};
+    const uint64_t units = std::accumulate(n_host, n_host + batch, (uint64_t)0);
+    SRS_LAUNCH_TIMED("msm_accum0", units, (k_accum0<C>), (ceil_div(h.cap0, ACC_THREADS), batch), (ACC_THREADS), 0, stream,
+                     (const uint32_t *)b.sorted, (size_t)h.M, p.plan, p.plan_stride, (const uint16_t *)b.tb, p.stride0,
+                     (const affine_t *)k.table, p.ping, p.stride0, 1u << h.l0_log, p.link);
+    accum_levels<C>(p, h, NBUCKET + 1, batch, stream);
+    SRS_LAUNCH((k_accum_final<C>), (NBUCKET / (FINAL_THREADS / 64), batch), (FINAL_THREADS), 0, stream, (const xyzz_t *)p.ping, p.stride0,
+               (const xyzz_t *)p.pong, p.stride1, p.plan, p.plan_stride, b.buckets, p.link);
+    const xyzz_t *red_from = b.buckets;
     int from_buckets = 0;
     if (fold != FOLD_NONE) {
         if (!k.fold_buckets) SRS_HIP_CHECK(hipMalloc((void **)&k.fold_buckets, (size_t)NBUCKET * sizeof(xyzz_t)));
-        SRS_LAUNCH((k_bucket_fold<C>), (NBUCKET / 64), (64), 0, stream, (const xyzz_t *)buckets, (const xyzz_t *)ping, (const xyzz_t *)pong,
-                   (const uint32_t *)plan, plan_stride, k.fold_buckets, fold == FOLD_FIRST ? 1 : 0);
+        SRS_LAUNCH((k_bucket_fold<C>), (NBUCKET / 64), (64), 0, stream, (const xyzz_t *)b.buckets, (const xyzz_t *)p.ping,
+                   (const xyzz_t *)p.pong, p.plan, p.plan_stride, k.fold_buckets, fold == FOLD_FIRST ? 1 : 0);
         if (fold != FOLD_LAST) return true;                  // no reduction, no result for this set
         red_from = k.fold_buckets;
         from_buckets = 1;
     }
-    SRS_LAUNCH((k_rowcol<C>), (RED_ROWS / 2 + RED_COLS, batch), (128), 0, stream, red_from,
-               (const xyzz_t *)ping, (size_t)parts0_cap, (const xyzz_t *)pong, (size_t)parts1_cap, (const uint32_t *)plan,
-               plan_stride, rc, no_link, from_buckets);
-    SRS_LAUNCH((k_reduce_final<C>), (3, batch), (RED_THREADS), 0, stream, (const xyzz_t *)rc, d_out);
-    if (!k.h_result) SRS_HIP_CHECK(hipHostMalloc(&k.h_result, 3 * (size_t)BATCH_ARGS * LANDING_SLOTS * sizeof(xyzz_t)));
-    xyzz_t *two = static_cast<xyzz_t *>(k.h_result) + 3 * (size_t)BATCH_ARGS * slot;
-    SRS_HIP_CHECK(hipMemcpyAsync(two, d_out, 3 * (size_t)batch * sizeof(xyzz_t), hipMemcpyDeviceToHost, stream));
-    k.slot_wide[slot] = false;
+    reduce_buckets<C>(p, batch, red_from, from_buckets, b.rc, 3, b.d_out, stream);
+    land(k, b.d_out, 3 * (size_t)batch, slot, stream);
+    k.landing[slot].wide = false;
     return true;
 }
 
 static bool use_wide(const Key &k, uint32_t n_max, uint32_t batch);
-// ---- slot mode: host side -------------------------------------------------------------------------------------------------------
-static uint32_t slot_log() {
-    const int64_t lg = tuning::get_or(tuning::MSM_SLOT_LOG, 0);
-    return (lg >= 2 && lg <= 8) ? (uint32_t)lg : SLOT_LOG;
-}
-// the part length a large set prefers when its buckets would fit shorter parts: 2^4
-static uint32_t slot_want_cap() { return 4u; }
+// ---- slot mode ------------------------------------------------------------------------------------------------------------------
 // Slot mode is for the sets of a CHUNKED commit (fold != FOLD_NONE): that is where every set used to pay its own accumulation levels, wave-level
 // pass and bucket fold.  A set that is a whole MSM keeps the r03 flow, by measurement (profiles/r04_ab_slots_cuts.txt): the batched
 // cross-term commitments would each pay a slot reduction (k = 17 Sangria step 6.02 vs 5.76 ms), a single 2^24 MSM is 2 % slower (22.3 vs
@@ -1972,57 +2145,16 @@ static bool use_slots(const Key &k, uint32_t n_max, uint32_t batch, Fold fold) {
     if (fold != FOLD_NONE) return batch == 1;
     return mode == 2 && !use_wide(k, n_max, batch);
 }
-struct SlotShape {
-    uint32_t S, nred;          // slots per bucket; reduction levels at the end of a commit (8 inputs per output)
-    uint64_t M, cap, cap1;     // digit slots; level-0 threads = overflow parts (worst case); parts after the first overflow level
-    int levels;                // overflow levels incl. level 0
-    size_t plan_stride;
-};
-static SlotShape slot_shape(uint32_t n_max) {
-    SlotShape h;
-    h.S = 1u << slot_log();
-    h.nred = (slot_log() + 2) / 3;
-    h.M = (uint64_t)n_max * NWIN;
-    // parts = sum_b ceil(c_b / L0) <= E / L0 + NBUCKET, and k_plan_s picks L0 >= (mean load) / (S - 1): never more than NBUCKET * S parts;
-    // L0 >= 2^SLOT_L0_MIN_LOG bounds them for small sets
-    h.cap = std::min<uint64_t>((uint64_t)NBUCKET * h.S, (h.M >> SLOT_L0_MIN_LOG) + NBUCKET);
-    h.cap1 = h.cap / ACC_L1 + NBUCKET + 1;
-    uint64_t parts = h.cap;
-    h.levels = 1;
-    while (parts > FINAL_FANIN && h.levels < MAX_LEVELS) {
-        parts = (parts + ACC_L1 - 1) / ACC_L1;
-        ++h.levels;
-    }
-    h.plan_stride = (size_t)(h.levels + 2) * (NBUCKET + 1) + 4;
-    return h;
-}
-static size_t workspace_bytes_slots(uint32_t n_max, uint32_t batch) {
-    const SlotShape h = slot_shape(n_max);
-    size_t per = 0;
-    per += Arena::pad(h.M * sizeof(uint16_t)) + Arena::pad(h.M * sizeof(uint32_t));          // digits, sorted
-    per += 2 * Arena::pad(NBUCKET * sizeof(uint32_t)) + Arena::pad(h.plan_stride * sizeof(uint32_t));
-    per += Arena::pad(h.cap * sizeof(xyzz_t)) + Arena::pad(h.cap * sizeof(uint16_t)) + Arena::pad(h.cap1 * sizeof(xyzz_t));   // overflow parts, map, pong
-    per += Arena::pad((size_t)NBUCKET * (h.S / 8 + 1) * sizeof(xyzz_t)) + Arena::pad((size_t)NBUCKET * (h.S / 64 + 1) * sizeof(xyzz_t));   // reduction ping / pong
-    per += Arena::pad((RED_ROWS + RED_COLS) * sizeof(xyzz_t));
-    if (use_two_pass(h.M, batch)) {
-        per += Arena::pad(h.M * sizeof(uint16_t)) + Arena::pad(h.M * sizeof(uint32_t));
-        per += Arena::pad((size_t)SEG * (SORT_TARGET_BLOCKS + 2 * NWIN) * sizeof(uint32_t));
-    }
-    return per * batch + Arena::pad(3 * batch * sizeof(xyzz_t)) + 8192;
-}
 
 // one set of <= BATCH_ARGS MSMs in slot mode.  fold: NONE = a whole commit (first and last set), FIRST / MIDDLE / LAST = the sets of a
 // chunked commit (batch == 1): only the last one reduces the slots and lands the 3 partial sums.
 template <class C>
 static bool enqueue_slots_t(Key &k, const fe_t *const *scalars_dev, const uint32_t *n_host, const uint32_t *base_host, uint32_t batch,
-                            int is_mont, hipStream_t stream, uint32_t slot, Fold fold) {
-    uint32_t n_max = 0;
-    for (uint32_t m = 0; m < batch; ++m) n_max = std::max(n_max, n_host[m]);
+                            uint32_t n_max, int is_mont, hipStream_t stream, uint32_t slot, Fold fold) {
     if (n_max == 0) return false;
     const bool first = fold == FOLD_NONE || fold == FOLD_FIRST, last = fold == FOLD_NONE || fold == FOLD_LAST;
-    const SlotShape h = slot_shape(n_max);
+    const SlotShape h = slot_shape(n_max, batch);
     const uint32_t S = h.S;
-    const uint64_t M = h.M;
     if (first) {
         k.slot_s = S;
         k.seq = 0;
@@ -2048,90 +2180,29 @@ static bool enqueue_slots_t(Key &k, const fe_t *const *scalars_dev, const uint32
     uint8_t *used_next = k.used + (size_t)((k.seq + 1) & 1u) * BATCH_ARGS * NBUCKET;
     ++k.seq;
 
-    Arena &A = k.arena;
-    A.reserve(workspace_bytes_slots(n_max, batch));
-    A.reset();
-    xyzz_t *d_out = A.take<xyzz_t>(3 * (size_t)batch);
-    uint16_t *dig = A.take<uint16_t>(M * batch);
-    uint32_t *sorted = A.take<uint32_t>(M * batch);
-    uint32_t *count = A.take<uint32_t>((size_t)NBUCKET * batch);
-    uint32_t *cursor = A.take<uint32_t>((size_t)NBUCKET * batch);
-    uint32_t *plan = A.take<uint32_t>(h.plan_stride * batch);
-    xyzz_t *ping = A.take<xyzz_t>(h.cap * batch);
-    uint16_t *tb = A.take<uint16_t>(h.cap * batch);
-    xyzz_t *pong = A.take<xyzz_t>(h.cap1 * batch);
-    xyzz_t *red_a = A.take<xyzz_t>((size_t)NBUCKET * (S / 8 + 1) * batch);
-    xyzz_t *red_b = A.take<xyzz_t>((size_t)NBUCKET * (S / 64 + 1) * batch);
-    xyzz_t *rc = A.take<xyzz_t>((size_t)(RED_ROWS + RED_COLS) * batch);
-    const bool two_pass = use_two_pass(M, batch);
-    uint16_t *gkey = two_pass ? A.take<uint16_t>(M * batch) : nullptr;
-    uint32_t *gpay = two_pass ? A.take<uint32_t>(M * batch) : nullptr;
-    uint32_t *tile_hist = two_pass ? A.take<uint32_t>((size_t)SEG * (SORT_TARGET_BLOCKS + 2 * NWIN) * batch) : nullptr;
-
-    BatchDesc bd;
-    for (uint32_t m = 0; m < BATCH_ARGS; ++m) {
-        bd.ptr[m] = m < batch ? scalars_dev[m] : nullptr;
-        bd.n[m] = m < batch ? n_host[m] : 0;
-        bd.base[m] = (m < batch && base_host) ? base_host[m] : 0;
-    }
-    const uint32_t s_rank = k.compact_scalars ? 0u : k.rank, s_world = k.compact_scalars ? 1u : k.world;
-    uint32_t tile = (uint32_t)(((uint64_t)n_max * NWIN * batch + SORT_TARGET_BLOCKS - 1) / SORT_TARGET_BLOCKS);
-    tile = (tile + 1023u) & ~1023u;
-    if (tile < SORT_TILE_MIN) tile = SORT_TILE_MIN;
-    const uint32_t tiles = ceil_div(n_max, tile);
-    uint32_t *h_ovf = k.h_ovf + (size_t)slot * BATCH_ARGS;
-    const uint32_t arr = (uint32_t)h.levels + 1;
-    SRS_LAUNCH((k_digits<C>), (ceil_div(n_max, 256), batch), (256), 0, stream, bd, dig, (size_t)M, is_mont, s_rank, s_world, count,
-               (uint32_t)(NBUCKET * batch));
-    SRS_LAUNCH(k_hist, (tiles, NWIN, batch), (SORT_THREADS), 0, stream, (const uint16_t *)dig, (size_t)M,
-               bd, count, tile, two_pass ? tile_hist : (uint32_t *)nullptr);
-    SRS_LAUNCH(k_plan_s, (batch, h.levels + 2), (PLAN_THREADS), 0, stream, (const uint32_t *)count, cursor, plan, h.plan_stride, h.levels, S,
-               (uint32_t)ACC_L1_LOG, used_prev, used_next, first ? 1 : 0, h_ovf, slot_want_cap());
-    if (two_pass) {
-        const uint32_t T1 = tiles * NWIN;
-        SRS_LAUNCH(k_scan_seg, (SEG, batch), (1024), 0, stream, tile_hist, T1, (const uint32_t *)plan, h.plan_stride);
-        SRS_LAUNCH(k_group, (tiles, NWIN, batch), (SORT_THREADS), 0, stream, (const uint16_t *)dig, (size_t)M, bd,
-                   (const uint32_t *)tile_hist, gkey, gpay, (size_t)M, (uint32_t)k.len, tile, (const uint32_t *)plan, h.plan_stride, tb,
-                   (size_t)h.cap, (uint32_t)h.levels + 1);                 // + the thread -> bucket map (k_expand's work)
-        SRS_LAUNCH(k_scatter2, (8 * ceil_div(ceil_div(M, SORT_TILE2), 8), batch), (SORT_THREADS), 0, stream, (const uint16_t *)gkey,
-                   (const uint32_t *)gpay, (size_t)M, (const uint32_t *)plan, h.plan_stride, cursor, sorted, (size_t)M,
-                   (uint32_t)SORT_TILE2);
-    } else {
-        SRS_LAUNCH(k_scatter, (tiles, NWIN, batch), (SORT_THREADS), 0, stream, (const uint16_t *)dig, (size_t)M,
-                   bd, cursor, sorted, (size_t)M, (uint32_t)k.len, tile);
-    }
-    uint64_t units = 0;
-    for (uint32_t m = 0; m < batch; ++m) units += n_host[m];
-    const Link *no_link = nullptr;
-    if (!two_pass) SRS_LAUNCH(k_expand, (NBUCKET / 4, batch), (256), 0, stream, (const uint32_t *)plan, h.plan_stride, tb, (size_t)h.cap, no_link, arr);
-    SRS_LAUNCH_TIMED("msm_accum0", units, (k_accum0s<C>), (ceil_div(h.cap, ACC_THREADS), batch), (ACC_THREADS), 0, stream,
-                     (const uint32_t *)sorted, (size_t)M, (const uint32_t *)plan, h.plan_stride, arr, (const uint16_t *)tb, (size_t)h.cap,
-                     (const affine_t *)k.table, k.slots, S, used_prev, first ? 1 : 0, ping, (size_t)h.cap);
+    const SlotBufs b = carve(k.arena, [&](auto &A) { return slot_layout(A, h, batch); });
+    const uint32_t arr = (uint32_t)h.levels + 1;             // the plan array of the level-0 parts
+    sort_front<C>(k, h, b, scalars_dev, n_host, base_host, batch, n_max, is_mont, stream, [&] {
+        SRS_LAUNCH(k_plan_s, (batch, h.levels + 2), (PLAN_THREADS), 0, stream, (const uint32_t *)b.count, b.cursor, b.plan, h.plan_stride,
+                   h.levels, S, (uint32_t)ACC_L1_LOG, used_prev, used_next, first ? 1 : 0, k.h_ovf + (size_t)slot * BATCH_ARGS, slot_want_cap());
+    }, true, arr);
+    const Parts p{b.plan, h.plan_stride, b.ping, (size_t)h.cap0, b.pong, (size_t)h.cap1, nullptr};
+    const uint64_t units = std::accumulate(n_host, n_host + batch, (uint64_t)0);
+    SRS_LAUNCH_TIMED("msm_accum0", units, (k_accum0s<C>), (ceil_div(h.cap0, ACC_THREADS), batch), (ACC_THREADS), 0, stream,
+                     (const uint32_t *)b.sorted, (size_t)h.M, p.plan, p.plan_stride, arr, (const uint16_t *)b.tb, p.stride0,
+                     (const affine_t *)k.table, k.slots, S, used_prev, first ? 1 : 0, p.ping, p.stride0);
     if (k.commit_ovf) {                      // hot buckets expected: the parts beyond the slots go through the level kernels into slot S - 1
-        xyzz_t *cur = ping, *nxt = pong;
-        size_t cur_stride = h.cap, nxt_stride = h.cap1;
-        uint64_t cap = h.cap;
-        for (int level = 1; level < h.levels; ++level) {
-            cap = cap / ACC_L1 + NBUCKET + 1;
-            SRS_LAUNCH((k_accum1<C>), (ceil_div(std::max<uint64_t>(cap, 4 * std::min<uint64_t>(cap, acc1_quad_max())), ACC_THREADS), batch), (ACC_THREADS), 0, stream,
-                       (const xyzz_t *)cur, cur_stride, (const uint32_t *)plan, h.plan_stride, level, nxt, nxt_stride, (uint32_t)ACC_L1, no_link,
-                       acc1_quad_max());
-            std::swap(cur, nxt);
-            std::swap(cur_stride, nxt_stride);
-        }
-        SRS_LAUNCH((k_ovf_final<C>), (NBUCKET / (FINAL_THREADS / 64), batch), (FINAL_THREADS), 0, stream, (const xyzz_t *)ping, (size_t)h.cap,
-                   (const xyzz_t *)pong, (size_t)h.cap1, (const uint32_t *)plan, h.plan_stride, k.slots, S, first ? 1 : 0);
+        accum_levels<C>(p, h, NBUCKET + 1, batch, stream);
+        SRS_LAUNCH((k_ovf_final<C>), (NBUCKET / (FINAL_THREADS / 64), batch), (FINAL_THREADS), 0, stream, (const xyzz_t *)p.ping, p.stride0,
+                   (const xyzz_t *)p.pong, p.stride1, p.plan, p.plan_stride, k.slots, S, first ? 1 : 0);
     }
-    k.slot_mode[slot] = true;
+    k.landing[slot] = {false, true, k.commit_ovf, batch};
     ++k.stat_slot_sets;
-    k.slot_ovf_on[slot] = k.commit_ovf;
-    k.slot_batch[slot] = batch;
-    k.slot_wide[slot] = false;
     if (!last) return true;
     // the commit's one reduction: slots -> buckets (8 inputs per output and level), then the usual row / column sums
     const xyzz_t *in = k.slots;
     uint32_t in_pb = S;
-    xyzz_t *outs[2] = {red_a, red_b};
+    xyzz_t *outs[2] = {b.red_a, b.red_b};
     for (uint32_t l = 0; l < h.nred; ++l) {
         const uint32_t out_pb = (in_pb + 7) / 8, n_out = NBUCKET * out_pb;
         xyzz_t *out = outs[l & 1u];
@@ -2147,18 +2218,14 @@ static bool enqueue_slots_t(Key &k, const fe_t *const *scalars_dev, const uint32
         in = out;
         in_pb = out_pb;
     }
-    SRS_LAUNCH((k_rowcol<C>), (RED_ROWS / 2 + RED_COLS, batch), (128), 0, stream, in, (const xyzz_t *)ping, (size_t)h.cap,
-               (const xyzz_t *)pong, (size_t)h.cap1, (const uint32_t *)plan, h.plan_stride, rc, no_link, 1);
-    SRS_LAUNCH((k_reduce_final<C>), (3, batch), (RED_THREADS), 0, stream, (const xyzz_t *)rc, d_out);
-    if (!k.h_result) SRS_HIP_CHECK(hipHostMalloc(&k.h_result, 3 * (size_t)BATCH_ARGS * LANDING_SLOTS * sizeof(xyzz_t)));
-    xyzz_t *two = static_cast<xyzz_t *>(k.h_result) + 3 * (size_t)BATCH_ARGS * slot;
-    SRS_HIP_CHECK(hipMemcpyAsync(two, d_out, 3 * (size_t)batch * sizeof(xyzz_t), hipMemcpyDeviceToHost, stream));
+    reduce_buckets<C>(p, batch, in, 1, b.rc, 3, b.d_out, stream);
+    land(k, b.d_out, 3 * (size_t)batch, slot, stream);
     return true;
 }
 
 bool overflow_missed(const Key &k, uint32_t slot) {
-    if (slot >= LANDING_SLOTS || !k.slot_mode[slot] || k.slot_ovf_on[slot] || !k.h_ovf) return false;
-    for (uint32_t m = 0; m < k.slot_batch[slot]; ++m)
+    if (slot >= LANDING_SLOTS || !k.landing[slot].slot_mode || k.landing[slot].ovf_on || !k.h_ovf) return false;
+    for (uint32_t m = 0; m < k.landing[slot].batch; ++m)
         if (k.h_ovf[(size_t)slot * BATCH_ARGS + m]) return true;
     return false;
 }
@@ -2167,11 +2234,11 @@ void note_commit(Key &k, const uint32_t *slots_used, uint32_t n_slots, uint64_t 
     uint64_t entries = 0;
     for (uint32_t i = 0; i < n_slots; ++i) {
         const uint32_t sl = slots_used[i];
-        if (sl >= LANDING_SLOTS || !k.slot_mode[sl] || !k.h_ovf) continue;
+        if (sl >= LANDING_SLOTS || !k.landing[sl].slot_mode || !k.h_ovf) continue;
         slot_sets = true;
-        for (uint32_t m = 0; m < k.slot_batch[sl]; ++m) entries += k.h_ovf[(size_t)(LANDING_SLOTS + sl) * BATCH_ARGS + m];
+        for (uint32_t m = 0; m < k.landing[sl].batch; ++m) entries += k.h_ovf[(size_t)(LANDING_SLOTS + sl) * BATCH_ARGS + m];
         bool hot = false;
-        for (uint32_t m = 0; m < k.slot_batch[sl]; ++m) hot = hot || k.h_ovf[(size_t)sl * BATCH_ARGS + m] != 0;
+        for (uint32_t m = 0; m < k.landing[sl].batch; ++m) hot = hot || k.h_ovf[(size_t)sl * BATCH_ARGS + m] != 0;
         if (hot) ++k.stat_hot_sets;
         any = any || hot;
     }
@@ -2195,43 +2262,6 @@ void note_commit(Key &k, const uint32_t *slots_used, uint32_t n_slots, uint64_t 
 }
 
 // ---- the wide-window pipeline: ONE MSM of n >= 2^WIDE_MIN_N_LOG scalars over table_w -------------------------------------
-struct WideShape {
-    uint64_t M;                // entry capacity = n * NWIN_W
-    int levels;
-    uint32_t l0_log, T, tiles_g;
-    size_t plan_stride;
-    uint64_t parts0_cap, parts1_cap;
-};
-static WideShape wide_shape(uint32_t n) {
-    WideShape w;
-    w.M = (uint64_t)n * NWIN_W;
-    w.levels = levels_for(w.M);                              // worst case: every entry in one bucket of one segment
-    w.l0_log = l0_log_for(w.M);
-    w.plan_stride = (size_t)(w.levels + 1) * (NBUCKET + 1) + 4;
-    w.parts0_cap = (w.M >> w.l0_log) + (uint64_t)NSEG_W * (NBUCKET + 1);
-    w.parts1_cap = w.parts0_cap / ACC_L1 + (uint64_t)NSEG_W * (NBUCKET + 1);
-    w.T = ceil_div(n, WIDE_TILE);
-    w.tiles_g = SORT_TARGET_BLOCKS;                          // the tile size is chosen on the device (k_seg_scan) so that this many suffice
-    return w;
-}
-static size_t workspace_bytes_wide(uint32_t n) {
-    const WideShape w = wide_shape(n);
-    size_t b = 0;
-    b += Arena::pad((4 + 4 * NSEG_W) * sizeof(xyzz_t));                          // results
-    b += Arena::pad(w.M * sizeof(uint16_t)) + 2 * Arena::pad(w.M * sizeof(uint32_t));   // grouped keys / payloads, sorted
-    b += Arena::pad(w.M * sizeof(uint16_t)) + Arena::pad(w.M * sizeof(uint32_t));       // ... grouped again by sub-segment (two-pass sort)
-    b += Arena::pad((size_t)SEG * w.tiles_g * sizeof(uint32_t));                 // per-tile sub-segment counts
-    b += Arena::pad((size_t)NSEG_W * w.T * sizeof(uint32_t));                    // per-tile segment counts
-    b += Arena::pad(4 * (NSEG_W + 2) * sizeof(uint32_t)) + Arena::pad(sizeof(Link));
-    b += 2 * Arena::pad((size_t)NSEG_W * NBUCKET * sizeof(uint32_t));            // count, cursor
-    b += Arena::pad(w.plan_stride * NSEG_W * sizeof(uint32_t));
-    b += Arena::pad(w.parts0_cap * sizeof(xyzz_t)) + Arena::pad(w.parts0_cap * sizeof(uint16_t));   // ping, map
-    b += Arena::pad(w.parts1_cap * sizeof(xyzz_t));                              // pong
-    b += Arena::pad((size_t)NSEG_W * NBUCKET * sizeof(xyzz_t));                  // buckets
-    b += Arena::pad((size_t)NSEG_W * (RED_ROWS + RED_COLS) * sizeof(xyzz_t));
-    return b + 4096;
-}
-
 static bool use_wide(const Key &k, uint32_t n_max, uint32_t batch) {
     const int min_log = (int)tuning::get_or(tuning::MSM_WIDE_MIN, (int64_t)WIDE_MIN_N_LOG);
     return k.table_w != nullptr && batch == 1 && n_max >= (1u << min_log);
@@ -2240,30 +2270,8 @@ static bool use_wide(const Key &k, uint32_t n_max, uint32_t batch) {
 template <class C>
 static bool enqueue_wide_t(Key &k, const fe_t *scalars_dev, uint32_t n, uint32_t base, int is_mont, hipStream_t stream, uint32_t slot) {
     const WideShape w = wide_shape(n);
-    Arena &A = k.arena;
-    A.reserve(workspace_bytes_wide(n));
-    A.reset();
-    xyzz_t *d_out = A.take<xyzz_t>(4);
-    xyzz_t *d_seg = A.take<xyzz_t>(4 * NSEG_W);
-    uint16_t *gkey = A.take<uint16_t>(w.M);
-    uint32_t *gpay = A.take<uint32_t>(w.M);
-    uint32_t *sorted = A.take<uint32_t>(w.M);
-    uint32_t *tile_cnt = A.take<uint32_t>((size_t)NSEG_W * w.T);
-    // the counting sort inside the segments: two passes through LDS (k_group_g + k_scatter2_g)
-    uint16_t *gkey2 = A.take<uint16_t>(w.M);
-    uint32_t *gpay2 = A.take<uint32_t>(w.M);
-    uint32_t *tile_hist = A.take<uint32_t>((size_t)SEG * w.tiles_g);
-    uint32_t *seg3 = A.take<uint32_t>(4 * (NSEG_W + 2));
-    uint32_t *seg_total = seg3, *seg_off = seg3 + (NSEG_W + 2), *tile_base = seg3 + 2 * (NSEG_W + 2), *tile_base2 = seg3 + 3 * (NSEG_W + 2);
-    Link *link = A.take<Link>(1);
-    uint32_t *count = A.take<uint32_t>((size_t)NSEG_W * NBUCKET);
-    uint32_t *cursor = A.take<uint32_t>((size_t)NSEG_W * NBUCKET);
-    uint32_t *plan = A.take<uint32_t>(w.plan_stride * NSEG_W);
-    xyzz_t *ping = A.take<xyzz_t>(w.parts0_cap);
-    uint16_t *tb = A.take<uint16_t>(w.parts0_cap);
-    xyzz_t *pong = A.take<xyzz_t>(w.parts1_cap);
-    xyzz_t *buckets = A.take<xyzz_t>((size_t)NSEG_W * NBUCKET);
-    xyzz_t *rc = A.take<xyzz_t>((size_t)NSEG_W * (RED_ROWS + RED_COLS));
+    const WideBufs b = carve(k.arena, [&](auto &A) { return wide_layout(A, w); });
+    uint32_t *seg_total = b.seg3, *seg_off = b.seg3 + (NSEG_W + 2), *tile_base = b.seg3 + 2 * (NSEG_W + 2), *tile_base2 = b.seg3 + 3 * (NSEG_W + 2);
 
     WideDesc wd;
     wd.ptr = scalars_dev;
@@ -2276,48 +2284,37 @@ static bool enqueue_wide_t(Key &k, const fe_t *scalars_dev, uint32_t n, uint32_t
 
     // sort: segment counts -> offsets -> grouping (MSD pass), then the counting sort inside the segments
     SRS_HIP_CHECK(hipMemsetAsync(seg_total, 0, (NSEG_W + 1) * sizeof(uint32_t), stream));
-    SRS_HIP_CHECK(hipMemsetAsync(count, 0, (size_t)NSEG_W * NBUCKET * sizeof(uint32_t), stream));
-    SRS_LAUNCH((k_seg_pass<C, false>), (w.T), (WIDE_THREADS), 0, stream, wd, tile_cnt, w.T, seg_total, (uint16_t *)nullptr,
+    SRS_HIP_CHECK(hipMemsetAsync(b.count, 0, (size_t)NSEG_W * NBUCKET * sizeof(uint32_t), stream));
+    SRS_LAUNCH((k_seg_pass<C, false>), (w.T), (WIDE_THREADS), 0, stream, wd, b.tile_cnt, w.T, seg_total, (uint16_t *)nullptr,
                (uint32_t *)nullptr, table_stride);
     const uint32_t small_tiles = (w.M >> 19) < 64 ? 1u : 0u, tile2_host = small_tiles ? SORT_TILE2 / 4 : SORT_TILE2;
-    SRS_LAUNCH(k_seg_scan, (NSEG_W), (1024), 0, stream, tile_cnt, w.T, (const uint32_t *)seg_total, seg_off, tile_base, tile_base2, small_tiles);
-    SRS_LAUNCH((k_seg_pass<C, true>), (w.T), (WIDE_THREADS), 0, stream, wd, tile_cnt, w.T, seg_total, gkey, gpay, table_stride);
-    SRS_LAUNCH(k_hist_g, (w.tiles_g), (SORT_THREADS), 0, stream, (const uint16_t *)gkey, (const uint32_t *)seg_off,
-               (const uint32_t *)tile_base, count, tile_hist);
-    SRS_LAUNCH(k_plan, (NSEG_W, w.levels + 1), (PLAN_THREADS), 0, stream, (const uint32_t *)count, cursor, plan, w.plan_stride, w.levels, w.l0_log,
-               (uint32_t)ACC_L1_LOG, (const uint32_t *)seg_off);
-    SRS_LAUNCH(k_scan_seg_g, (SEG, NSEG_W), (1024), 0, stream, tile_hist, w.tiles_g, (const uint32_t *)tile_base, (const uint32_t *)plan,
+    SRS_LAUNCH(k_seg_scan, (NSEG_W), (1024), 0, stream, b.tile_cnt, w.T, (const uint32_t *)seg_total, seg_off, tile_base, tile_base2, small_tiles);
+    SRS_LAUNCH((k_seg_pass<C, true>), (w.T), (WIDE_THREADS), 0, stream, wd, b.tile_cnt, w.T, seg_total, b.gkey, b.gpay, table_stride);
+    SRS_LAUNCH(k_hist_g, (w.tiles_g), (SORT_THREADS), 0, stream, (const uint16_t *)b.gkey, (const uint32_t *)seg_off,
+               (const uint32_t *)tile_base, b.count, b.tile_hist);
+    SRS_LAUNCH(k_plan, (NSEG_W, w.levels + 1), (PLAN_THREADS), 0, stream, (const uint32_t *)b.count, b.cursor, b.plan, w.plan_stride, w.levels,
+               w.l0_log, (uint32_t)ACC_L1_LOG, (const uint32_t *)seg_off);
+    SRS_LAUNCH(k_scan_seg_g, (SEG, NSEG_W), (1024), 0, stream, b.tile_hist, w.tiles_g, (const uint32_t *)tile_base, (const uint32_t *)b.plan,
                w.plan_stride);
-    SRS_LAUNCH(k_group_g, (w.tiles_g), (SORT_THREADS), 0, stream, (const uint16_t *)gkey, (const uint32_t *)gpay, (const uint32_t *)seg_off,
-               (const uint32_t *)tile_base, (const uint32_t *)tile_hist, gkey2, gpay2);
+    SRS_LAUNCH(k_group_g, (w.tiles_g), (SORT_THREADS), 0, stream, (const uint16_t *)b.gkey, (const uint32_t *)b.gpay, (const uint32_t *)seg_off,
+               (const uint32_t *)tile_base, (const uint32_t *)b.tile_hist, b.gkey2, b.gpay2);
     // tiles of SORT_TILE2 entries cut per segment: at most M / SORT_TILE2 + NSEG_W of them; 8 x ceil(. / 8) workgroups (XCD mapping)
-    SRS_LAUNCH(k_scatter2_g, (8 * ceil_div(ceil_div(w.M, tile2_host) + NSEG_W, 8)), (SORT_THREADS), 0, stream, (const uint16_t *)gkey2,
-               (const uint32_t *)gpay2, (const uint32_t *)seg_off, (const uint32_t *)tile_base2, cursor, sorted);
-    SRS_LAUNCH(k_link, (1), (64), 0, stream, (const uint32_t *)plan, w.plan_stride, w.levels, link);
-    const Link *lk = link;
-    SRS_LAUNCH(k_expand, (NBUCKET / 4, NSEG_W), (256), 0, stream, (const uint32_t *)plan, w.plan_stride, tb, (size_t)0, lk, 1u);
-    SRS_LAUNCH_TIMED("msm_accum0", n, (k_accum0<C>), (ceil_div(w.parts0_cap, ACC_THREADS)), (ACC_THREADS), 0, stream, (const uint32_t *)sorted,
-                     (size_t)0, (const uint32_t *)plan, w.plan_stride, (const uint16_t *)tb, (size_t)0, (const affine_t *)k.table_w, ping, (size_t)0,
-                     1u << w.l0_log, lk);
-    xyzz_t *cur = ping, *nxt = pong;
-    uint64_t cap = w.parts0_cap;
-    for (int level = 1; level < w.levels; ++level) {
-        cap = cap / ACC_L1 + (uint64_t)NSEG_W * (NBUCKET + 1);
-        SRS_LAUNCH((k_accum1<C>), (ceil_div(std::max<uint64_t>(cap, 4 * std::min<uint64_t>(cap, acc1_quad_max())), ACC_THREADS)), (ACC_THREADS), 0,
-                   stream, (const xyzz_t *)cur, (size_t)0, (const uint32_t *)plan, w.plan_stride, level, nxt, (size_t)0, (uint32_t)ACC_L1, lk,
-                   acc1_quad_max());
-        std::swap(cur, nxt);
-    }
-    SRS_LAUNCH((k_accum_final<C>), (NBUCKET / (FINAL_THREADS / 64), NSEG_W), (FINAL_THREADS), 0, stream, (const xyzz_t *)ping, (size_t)0,
-               (const xyzz_t *)pong, (size_t)0, (const uint32_t *)plan, w.plan_stride, buckets, lk);
-    SRS_LAUNCH((k_rowcol<C>), (RED_ROWS / 2 + RED_COLS, NSEG_W), (128), 0, stream, (const xyzz_t *)buckets, (const xyzz_t *)ping, (size_t)0,
-               (const xyzz_t *)pong, (size_t)0, (const uint32_t *)plan, w.plan_stride, rc, lk, 0);
-    SRS_LAUNCH((k_reduce_final<C>), (4, NSEG_W), (RED_THREADS), 0, stream, (const xyzz_t *)rc, d_seg);
-    SRS_LAUNCH((k_wide_combine<C>), (1), (256), 0, stream, (const xyzz_t *)d_seg, d_out);
-    if (!k.h_result) SRS_HIP_CHECK(hipHostMalloc(&k.h_result, 3 * (size_t)BATCH_ARGS * LANDING_SLOTS * sizeof(xyzz_t)));
-    xyzz_t *land = static_cast<xyzz_t *>(k.h_result) + 3 * (size_t)BATCH_ARGS * slot;
-    SRS_HIP_CHECK(hipMemcpyAsync(land, d_out, 4 * sizeof(xyzz_t), hipMemcpyDeviceToHost, stream));
-    k.slot_wide[slot] = true;
+    SRS_LAUNCH(k_scatter2_g, (8 * ceil_div(ceil_div(w.M, tile2_host) + NSEG_W, 8)), (SORT_THREADS), 0, stream, (const uint16_t *)b.gkey2,
+               (const uint32_t *)b.gpay2, (const uint32_t *)seg_off, (const uint32_t *)tile_base2, b.cursor, b.sorted);
+    SRS_LAUNCH(k_link, (1), (64), 0, stream, (const uint32_t *)b.plan, w.plan_stride, w.levels, b.link);
+    // from here on the 16 segments are ONE linked batch: no strides, the link says where a segment's parts start
+    const Parts p{b.plan, w.plan_stride, b.ping, 0, b.pong, 0, b.link};
+    SRS_LAUNCH(k_expand, (NBUCKET / 4, NSEG_W), (256), 0, stream, p.plan, p.plan_stride, b.tb, (size_t)0, p.link, 1u);
+    SRS_LAUNCH_TIMED("msm_accum0", n, (k_accum0<C>), (ceil_div(w.cap0, ACC_THREADS)), (ACC_THREADS), 0, stream, (const uint32_t *)b.sorted,
+                     (size_t)0, p.plan, p.plan_stride, (const uint16_t *)b.tb, (size_t)0, (const affine_t *)k.table_w, p.ping, (size_t)0,
+                     1u << w.l0_log, p.link);
+    accum_levels<C>(p, w, (uint64_t)NSEG_W * (NBUCKET + 1), 1, stream);
+    SRS_LAUNCH((k_accum_final<C>), (NBUCKET / (FINAL_THREADS / 64), NSEG_W), (FINAL_THREADS), 0, stream, (const xyzz_t *)p.ping, p.stride0,
+               (const xyzz_t *)p.pong, p.stride1, p.plan, p.plan_stride, b.buckets, p.link);
+    reduce_buckets<C>(p, NSEG_W, b.buckets, 0, b.rc, 4, b.d_seg, stream);
+    SRS_LAUNCH((k_wide_combine<C>), (1), (256), 0, stream, (const xyzz_t *)b.d_seg, b.d_out);
+    land(k, b.d_out, 4, slot, stream);
+    k.landing[slot].wide = true;
     return true;
 }
 
@@ -2333,7 +2330,7 @@ static void finish_t(Key &k, uint32_t batch, uint32_t slot, bool launched, xyzz_
     using F = typename C::F;
     fe_t c = F::one();
     for (int d = 0; d < 5; ++d) c = F::halve(c);
-    std::vector<xyzz_t> two(3 * (size_t)batch + (k.slot_wide[slot] ? 1 : 0));
+    std::vector<xyzz_t> two(3 * (size_t)batch + (k.landing[slot].wide ? 1 : 0));
     for (size_t i = 0; i < two.size(); ++i) {
         two[i].x = F::mul(raw[i].x, c);
         two[i].y = F::mul(raw[i].y, c);
@@ -2345,14 +2342,12 @@ static void finish_t(Key &k, uint32_t batch, uint32_t slot, bool launched, xyzz_
         for (uint32_t j = 1; j < RED_COLS; j <<= 1) a = Ec<C>::dbl(a);
         result_host[m] = Ec<C>::add(a, two[3 * m + 1]);
     }
-    if (k.slot_wide[slot]) {                                 // one MSM, 4 sums: + NBUCKET * U for the segment totals
+    if (k.landing[slot].wide) {                                 // one MSM, 4 sums: + NBUCKET * U for the segment totals
         xyzz_t u = two[3];
         for (uint32_t j = 1; j < NBUCKET; j <<= 1) u = Ec<C>::dbl(u);
         result_host[0] = Ec<C>::add(result_host[0], u);
     }
 }
-
-bool may_fold(const Key &, uint32_t) { return true; }      // (r03: not for sets that took the wide pipeline; they no longer do)
 
 bool enqueue(Key &k, const fe_t *const *scalars_dev, const uint32_t *n_host, const uint32_t *base_host, uint32_t batch, int is_mont,
              hipStream_t stream, uint32_t slot, Fold fold) {
@@ -2366,7 +2361,7 @@ bool enqueue(Key &k, const fe_t *const *scalars_dev, const uint32_t *n_host, con
     }
     if (batch == 1 && fold == FOLD_NONE && use_wide(k, n_host[0], 1)) {      // the sets of a chunked commit stay on the 16-bit windows
         const uint32_t base = base_host ? base_host[0] : 0;
-        k.slot_mode[slot] = false;
+        k.landing[slot].slot_mode = false;
         ++k.stat_other_sets;
         return k.curve == 0 ? enqueue_wide_t<Bn256>(k, scalars_dev[0], n_host[0], base, is_mont, stream, slot)
                             : enqueue_wide_t<Grumpkin>(k, scalars_dev[0], n_host[0], base, is_mont, stream, slot);
@@ -2377,13 +2372,13 @@ bool enqueue(Key &k, const fe_t *const *scalars_dev, const uint32_t *n_host, con
     const bool first = fold == FOLD_NONE || fold == FOLD_FIRST;
     const bool slots = first ? use_slots(k, n_max, batch, fold) : k.slot_s != 0;
     if (slots)
-        return k.curve == 0 ? enqueue_slots_t<Bn256>(k, scalars_dev, n_host, base_host, batch, is_mont, stream, slot, fold)
-                            : enqueue_slots_t<Grumpkin>(k, scalars_dev, n_host, base_host, batch, is_mont, stream, slot, fold);
+        return k.curve == 0 ? enqueue_slots_t<Bn256>(k, scalars_dev, n_host, base_host, batch, n_max, is_mont, stream, slot, fold)
+                            : enqueue_slots_t<Grumpkin>(k, scalars_dev, n_host, base_host, batch, n_max, is_mont, stream, slot, fold);
     if (first) k.slot_s = 0;
-    k.slot_mode[slot] = false;
+    k.landing[slot].slot_mode = false;
     ++k.stat_other_sets;
-    return k.curve == 0 ? enqueue_t<Bn256>(k, scalars_dev, n_host, base_host, batch, is_mont, stream, slot, fold)
-                        : enqueue_t<Grumpkin>(k, scalars_dev, n_host, base_host, batch, is_mont, stream, slot, fold);
+    return k.curve == 0 ? enqueue_t<Bn256>(k, scalars_dev, n_host, base_host, batch, n_max, is_mont, stream, slot, fold)
+                        : enqueue_t<Grumpkin>(k, scalars_dev, n_host, base_host, batch, n_max, is_mont, stream, slot, fold);
 }
 void finish(Key &k, uint32_t batch, uint32_t slot, bool launched, xyzz_t *result_host) {
     if (k.curve == 0) finish_t<Bn256>(k, batch, slot, launched, result_host); else finish_t<Grumpkin>(k, batch, slot, launched, result_host);

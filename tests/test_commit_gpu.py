@@ -393,6 +393,20 @@ def test_commit_upload_chunked(srs, oracle, cid):
         assert r.returncode == 0 and "ok" in r.stdout, (chunks, r.stdout[-500:], r.stderr[-1500:])
 
 
+def test_commit_upload_chunked_bucket_fold(srs, oracle):
+    """A chunked commit with slot mode off (tuning msm_slots = 0): three chunks through the level kernels, their bucket sums folded into the
+    key's running buckets (k_bucket_fold FIRST / MIDDLE / LAST) and reduced once; both sort paths, both curves -- the program of
+    test_emu_chunked_commit_bucket_fold on the real library, same sizes, same statistics."""
+    import subprocess
+    import sys
+    from conftest import ROOT, tune_env
+    from fold_cases import bucket_fold_program
+    for sort in (1, 2):
+        r = subprocess.run([sys.executable, "-c", bucket_fold_program()], cwd=ROOT, env=tune_env(msm_slots=0, commit_chunks=3, msm_sort=sort),
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0 and "ok" in r.stdout, (sort, r.stdout[-500:], r.stderr[-1500:])
+
+
 def test_commit_upload_default_chunking_large(srs, oracle):
     """Default chunking (4 chunks from 2^22 scalars on) at a size with real overlap: additivity against plain commits."""
     import torch

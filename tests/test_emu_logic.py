@@ -600,6 +600,20 @@ def test_emu_slot_mode_commits():
         assert r.returncode == 0 and "ok" in r.stdout, (tag, r.stdout[-500:], r.stderr[-1500:])
 
 
+def test_emu_chunked_commit_bucket_fold():
+    """msm.hip without slot mode (tuning msm_slots = 0): the three chunks of a streamed commit take the level kernels and fold their bucket
+    sums into the key's running buckets (k_bucket_fold, roles FIRST / MIDDLE / LAST), the last one reduces them (k_rowcol from the buckets);
+    both sort paths, both curves, uniform and trace-like scalars (most entries in two buckets), against the oracle; msm_stats must show
+    six sets per key, none of them in slot mode, and no redo."""
+    import sys
+    from fold_cases import bucket_fold_program
+    subprocess.check_call(["make", "-C", EMU_DIR, "-j4"], stdout=subprocess.DEVNULL)
+    jobs = [(f"sort{sort}", [sys.executable, "-c", bucket_fold_program(EMU_LIB)], tune_env(msm_slots=0, commit_chunks=3, msm_sort=sort))
+            for sort in (1, 2)]
+    for tag, r in _run_all(jobs).items():
+        assert r.returncode == 0 and "ok" in r.stdout, (tag, r.stdout[-500:], r.stderr[-1500:])
+
+
 def test_emu_long_level0_parts():
     """msm.hip l0_log_for: 64 gathered additions per level-0 thread (the setting of large MSMs), forced on a small one."""
     import sys
