@@ -69,9 +69,10 @@ const char *srs_last_error(void);
 const char *srs_version(void);
 /* Run-time tunables (csrc/tuning.h holds the table): each selects among code paths the library takes by default for SOME input size
  * (or moves the size threshold between them); none changes a result.  Tests use them to run a large-input path on an input the CPU
- * oracle can check; a deployer may set "msm_wide" = 0 to save 13/16 of a large key's HBM (also: environment SRS_MSM_WIDE=0).
+ * oracle can check; a deployer may set "msm_wide" = 0 to save 13/16 of a large key's HBM (also: environment SRS_MSM_WIDE=0), or
+ * "msm_compact" = 1 before creating a key to halve its 16-bit-window table (8 windows + the curve endomorphism, srs_ck_is_compact).
  * Names (srs_tuning_name(i), i = 0, 1, ... until NULL): msm_sort, msm_l0, msm_wide, msm_wide_min, msm_slots, msm_slot_log,
- * msm_expect_ovf, msm_quad_max, commit_chunks, pg_f_eval, pg_g_fft, jit_always, no_jit.  Process-wide; set before the calls they
+ * msm_expect_ovf, msm_quad_max, commit_chunks, pg_f_eval, pg_g_fft, jit_always, no_jit, msm_compact.  Process-wide; set before the calls they
  * affect (a value is read when a call starts).  rc SRS_ERR_INVALID for an unknown name.  No reference counterpart. */
 int srs_tuning_set(const char *name, int64_t value);
 int srs_tuning_get(const char *name, int64_t *value);        /* *value = INT64_MIN while unset */
@@ -192,6 +193,21 @@ int srs_ck_msm_stats(const srs_ck *ck, uint64_t *out4);
  * device-resident MSMs of >= 2^23 scalars use it), 0 when it does not -- by size, by SRS_MSM_WIDE=0, or because the device could not hold
  * it (the key then works on the 16-bit windows alone).  Multi-device keys: 1 when every shard holds it. */
 int srs_ck_has_wide_table(const srs_ck *ck);
+/* Compact keys (tunable "msm_compact" = 1 when the key is created, by any creation entry; default 0).  bn256 G1 and grumpkin have the
+ * endomorphism phi(x, y) = (beta x, y) = [lambda](x, y): a scalar splits as k = k1 + lambda k2 with |k1|, |k2| < 2^127, so the upper
+ * eight windows of the table are phi of the lower eight.  A compact key stores 8 windows instead of 16 (half the HBM, half the
+ * expansion at creation), never builds the 20-bit table (MSMs of every size run on the 16-bit windows) and pays one field product
+ * per gathered point of the upper half.  Same results, same entries; srs_ck_get_bases / srs_ck_save_file are unchanged.
+ * srs_ck_is_compact: 1 / 0.  srs_ck_table_bytes: bytes of window tables (16-bit and 20-bit) this rank holds -- all shards of a
+ * multi-device key.  No reference counterpart. */
+int srs_ck_is_compact(const srs_ck *ck);
+size_t srs_ck_table_bytes(const srs_ck *ck);
+/* Host-only diagnostics of the split (no device needed, no reference counterpart).  srs_glv_constants: lambda (scalar field) and
+ * beta (base field) of `curve` as canonical integers, 4 x u64 little-endian.  srs_glv_decompose: k (repr as elsewhere) ->
+ * |k1|, |k2| (canonical integers) and their signs (1 = negative), by the very body the digit kernel runs:
+ * k = (-1)^neg1 |k1| + lambda (-1)^neg2 |k2| (mod the group order). */
+int srs_glv_constants(int curve, srs_fe *lambda, srs_fe *beta);
+int srs_glv_decompose(int curve, const srs_fe *k, int repr, srs_fe *k1_abs, srs_fe *k2_abs, int *neg1, int *neg2);
 /* Diagnostics of ONE shard of a multi-device key (shard < srs_ck_num_shards): out[0] = bytes its streamed commits brought up from host
  * memory over the shard's own link (srs_commit_upload on a multi-device key sends every shard ITS block-cyclic stripes only: n * 32 /
  * shards bytes per commit and link, in chunks that overlap the shard's MSM), out[1] = bytes it forwarded to the process's device to

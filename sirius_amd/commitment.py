@@ -127,6 +127,14 @@ class CommitmentKey:
         """True when the key holds the second (20-bit-window) table (srs_ck_has_wide_table)."""
         return bool(L.lib().srs_ck_has_wide_table(self._h))
 
+    def is_compact(self):
+        """True when the key stores 8 windows and uses the curve endomorphism for the other 8 (created under tuning msm_compact=1)."""
+        return bool(L.lib().srs_ck_is_compact(self._h))
+
+    def table_bytes(self):
+        """Bytes of window tables this key holds on its device(s) (srs_ck_table_bytes)."""
+        return int(L.lib().srs_ck_table_bytes(self._h))
+
     @classmethod
     def load_from_file(cls, curve, file_path, k, rank=0, world=1):
         """`CommitmentKey::load_from_file` + the on-curve validation of `load_or_setup_cache`

@@ -463,8 +463,9 @@ int create_multi(int curve, size_t len, int n_devices, Fill fill, srs_ck **out) 
                 }
             }
             SRS_HIP_CHECK(hipStreamCreateWithFlags(&sh->stream, hipStreamNonBlocking));
+            const size_t windows = msm::choose_windows(sh->key);      // the key's form, decided for empty shards too (srs_ck_is_compact)
             if (sh->key.len) {
-                SRS_HIP_CHECK(hipMalloc((void **)&sh->key.table, sh->key.len * msm::NWIN * sizeof(affine_t)));
+                SRS_HIP_CHECK(hipMalloc((void **)&sh->key.table, sh->key.len * windows * sizeof(affine_t)));
                 fill(*sh);
                 msm::build_table(sh->key, sh->stream);
             }
@@ -645,8 +646,9 @@ int srs_ck_create_sharded(int curve, const srs_affine *bases, size_t len, int sp
         ck->key.len = shard_count(len, rank, world);
         const size_t n = ck->key.len;
         try {
+            const size_t windows = msm::choose_windows(ck->key);      // the key's form, decided for an empty key or shard too
             if (n) {
-                SRS_HIP_CHECK(hipMalloc((void **)&ck->key.table, n * msm::NWIN * sizeof(affine_t)));
+                SRS_HIP_CHECK(hipMalloc((void **)&ck->key.table, n * windows * sizeof(affine_t)));
                 const hipMemcpyKind kind = space == SRS_SPACE_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
                 if (world == 1) {
                     SRS_HIP_CHECK(hipMemcpy(ck->key.table, bases, n * sizeof(affine_t), kind));
@@ -683,8 +685,9 @@ int srs_ck_setup_synthetic(int curve, size_t len, uint64_t seed, uint32_t rank, 
         ck->key.world = world;
         ck->key.len = shard_count(len, rank, world);
         try {
+            const size_t windows = msm::choose_windows(ck->key);
             if (ck->key.len) {
-                SRS_HIP_CHECK(hipMalloc((void **)&ck->key.table, ck->key.len * msm::NWIN * sizeof(affine_t)));
+                SRS_HIP_CHECK(hipMalloc((void **)&ck->key.table, ck->key.len * windows * sizeof(affine_t)));
                 msm::generate_bases(ck->key, seed, nullptr);
                 msm::build_table(ck->key, nullptr);
             }
@@ -882,6 +885,58 @@ int srs_ck_has_wide_table(const srs_ck *ck) {
     for (const auto &sh : ck->shards)
         if (sh->key.len && !sh->key.table_w) return 0;
     return 1;
+}
+
+int srs_ck_is_compact(const srs_ck *ck) {
+    if (!ck) return 0;
+    if (ck->shards.empty()) return ck->key.compact ? 1 : 0;
+    for (const auto &sh : ck->shards)
+        if (!sh->key.compact) return 0;
+    return 1;
+}
+size_t srs_ck_table_bytes(const srs_ck *ck) {
+    if (!ck) return 0;
+    if (ck->shards.empty()) return msm::table_bytes(ck->key);
+    size_t total = 0;
+    for (const auto &sh : ck->shards) total += msm::table_bytes(sh->key);
+    return total;
+}
+
+int srs_glv_constants(int curve, srs_fe *lambda, srs_fe *beta) {
+    if (!valid_curve(curve) || !lambda || !beta) return fail(SRS_ERR_INVALID, "srs_glv_constants: bad argument");
+    auto go = [&](auto tag) {
+        using K = GlvConsts<decltype(tag)::ID>;
+        fe_t l, b;
+        for (int i = 0; i < 8; ++i) {
+            l.v[i] = K::lambda(i);
+            b.v[i] = K::beta(i);
+        }
+        std::memcpy(lambda, &l, 32);
+        std::memcpy(beta, &b, 32);
+    };
+    if (curve == SRS_CURVE_BN256) go(Bn256{}); else go(Grumpkin{});
+    return SRS_OK;
+}
+int srs_glv_decompose(int curve, const srs_fe *k, int repr, srs_fe *k1_abs, srs_fe *k2_abs, int *neg1, int *neg2) {
+    if (!valid_curve(curve) || !k || !k1_abs || !k2_abs || !neg1 || !neg2) return fail(SRS_ERR_INVALID, "srs_glv_decompose: bad argument");
+    auto go = [&](auto tag) {
+        using C = decltype(tag);
+        fe_t s;
+        std::memcpy(&s, k, 32);
+        if (repr == SRS_REPR_MONT) s = C::S::from_mont(s);
+        const glv_t g = glv_decompose<C>(s);
+        fe_t a, b;
+        for (int i = 0; i < 8; ++i) {
+            a.v[i] = i < 4 ? g.k1[i] : 0u;
+            b.v[i] = i < 4 ? g.k2[i] : 0u;
+        }
+        std::memcpy(k1_abs, &a, 32);
+        std::memcpy(k2_abs, &b, 32);
+        *neg1 = g.neg1 ? 1 : 0;
+        *neg2 = g.neg2 ? 1 : 0;
+    };
+    if (curve == SRS_CURVE_BN256) go(Bn256{}); else go(Grumpkin{});
+    return SRS_OK;
 }
 
 void srs_ck_free(srs_ck *ck) {

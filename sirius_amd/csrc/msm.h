@@ -2,6 +2,7 @@
 #pragma once
 #include "curve.cuh"
 #include "devrt.h"
+#include "glv.cuh"
 #include "tuning.h"
 
 #include <cstdlib>
@@ -11,6 +12,8 @@ namespace msm {
 
 constexpr int WBITS = 16;                 // signed-digit window width
 constexpr int NWIN = 16;                  // ceil(256 / WBITS); scalars are < 2^254
+constexpr int NWIN_COMPACT = 8;           // windows a compact key stores: digit rows 8..15 are the windows 0..7 of phi(P) (glv.cuh)
+constexpr uint32_t PAY_ENDO = 1u << 30;   // compact keys: the entry's point is phi of the table entry (bit 31 is the sign, the index lies below)
 constexpr uint32_t NBUCKET = 1u << (WBITS - 1);   // |digit| in 1..2^15 -> bucket |digit|-1
 constexpr uint32_t STRIPE_LOG = 10;       // multi-GPU block-cyclic stripe (entries)
 
@@ -61,11 +64,15 @@ inline bool expect_ovf_initial() { return tuning::get_or(tuning::MSM_EXPECT_OVF,
 
 // Device-resident commitment key: window-expanded table T[w * len + i] = 2^(16 w) P_i, coordinates in the
 // R' = 2^261 Montgomery form of the 9 x 29-bit multiplier (field29.cuh) once build_table has run.
+// A COMPACT key (tuning msm_compact = 1 at creation) holds windows 0..7 only: a scalar is split k = k1 + lambda k2 (glv.cuh), digit rows
+// 0..7 are the digits of |k1|, rows 8..15 those of |k2|, and an entry of rows 8..15 gathers T[(w - 8) * len + i] with PAY_ENDO set:
+// the accumulation multiplies its x by beta.  Everything between the digits and level 0 sees the same 16 rows as for a full key.
 struct Key {
     int curve = 0;            // 0 bn256 G1, 1 grumpkin
     size_t len = 0;           // number of bases held by THIS rank
     size_t global_len = 0;    // length of the whole key (== len when world == 1)
     uint32_t rank = 0, world = 1;
+    bool compact = false;     // 8-window table + endomorphism (choose_windows, before the table is allocated)
     bool compact_scalars = false;   // world > 1: the scalar vectors handed to run() hold ONLY this rank's stripes, gathered (multi-device keys)
     affine_t *table = nullptr;
     affine_t *table_w = nullptr;   // T_w[w][i] = 2^(20 w) P_i, w < NWIN_W (keys of >= 2^WIDE_MIN_KEY_LOG bases; owned by the key: release())
@@ -92,8 +99,13 @@ struct Key {
     uint32_t cold_streak = 0;         // commits in a row without hot buckets while they were expected
 };
 
-// fills table[len .. 16*len) from table[0 .. len); keys that want it (wants_wide_table) also get table_w
+// decides the key's form from tuning msm_compact (read HERE, once per key) and returns the windows `table` must hold: every creation
+// entry allocates len * choose_windows(key) entries, fills window 0 and calls build_table
+int choose_windows(Key &k);
+// fills table[len .. windows * len) from table[0 .. len); full keys that want it (wants_wide_table) also get table_w
 void build_table(Key &k, hipStream_t stream);
+// bytes of window tables the key holds (table and table_w)
+size_t table_bytes(const Key &k);
 // frees what the key owns besides `table`: table_w and the run state
 void release(Key &k);
 // fills table[0 .. len) with the synthetic key (see k_gen_bases)

@@ -31,6 +31,9 @@
 // set (k_plan_s) picks the part length on the device; parts beyond the slots (hot buckets) go through the level kernels into the
 // bucket's last slot, launched only when the key expects them (msm.h: overflow_missed / note_commit).  Whole MSMs of >= 2^23 scalars
 // take the 13 x 20-bit "wide" windows over a second table (16 virtual MSMs of 2^15 buckets each).
+// Compact keys (tuning msm_compact = 1 at creation, msm.h): 8 stored windows; k_digits splits the scalar with the curve endomorphism
+// (glv.cuh), rows 8..15 gather phi of windows 0..7 -- the payload carries a flag, level 0 multiplies the gathered x by beta (k_accum0c /
+// k_accum0sc).  Everything between the digits and level 0, and everything after it, is shared with full keys.
 // Host driver (end of this file): enqueue() picks one of three flows (enqueue_t: levels, enqueue_slots_t: slot mode, enqueue_wide_t).  Each
 // computes its shape once (*_shape: sizes, grids and every tunable), carves the key's arena by its one buffer list (*_layout, also the
 // sizer behind reserve()) and runs the shared stages: sort_front, accum_levels, reduce_buckets, land.
@@ -206,7 +209,25 @@ struct BatchDesc {
     uint32_t base[BATCH_ARGS];      // first base of MSM m inside the key (0 for the usual prefix commit; chunked commits slide it)
 };
 
-template <class C>
+// compact keys: the 8 signed 16-bit digits of one half (|k| < 2^127, sign `neg`) of the split scalar, rows d[0], d[n], ..., d[7 n].
+// The half's sign goes into every digit, and the tie v = 0x8000 is broken by it: the code format holds digits -0x7FFF .. 0x8000, so a
+// negative half recodes |k| into -0x8000 .. 0x7FFF before negating.  The top digit never carries out (|k| < 2^127: its v <= 0x8000 only
+// when the bound were 2^127 itself; tools/gen_glv_consts.py proves < 2^126).
+__device__ __forceinline__ void recode_half(const uint32_t (&k)[4], bool neg, uint16_t *__restrict__ d, size_t n) {
+    const uint32_t top = neg ? 0x7FFFu : 0x8000u;     // largest v that stays a non-negative digit of |k|
+    uint32_t carry = 0;
+#pragma unroll
+    for (int w = 0; w < NWIN_COMPACT; ++w) {
+        const uint32_t v = ((k[w >> 1] >> ((w & 1) * 16)) & 0xFFFFu) + carry;
+        const bool borrow = v > top;
+        const uint32_t mag = borrow ? 0x10000u - v : v;
+        const bool minus = borrow != neg;              // sign of the digit of the SIGNED half
+        carry = borrow ? 1u : 0u;
+        d[(size_t)w * n] = (uint16_t)(mag ? ((mag - 1u) | (minus ? 0x8000u : 0u)) : 0xFFFFu);
+    }
+}
+
+template <class C, bool COMPACT>
 __global__ void k_digits(BatchDesc bd, uint16_t *__restrict__ dig, size_t dig_stride, int is_mont, uint32_t rank, uint32_t world,
                          uint32_t *__restrict__ count_zero, uint32_t n_zero) {
     using S = typename C::S;
@@ -221,6 +242,12 @@ __global__ void k_digits(BatchDesc bd, uint16_t *__restrict__ dig, size_t dig_st
     fe_t s = bd.ptr[m][shard_global_index(i, rank, world)];
     if (is_mont) s = S::from_mont(s);
     uint16_t *d = dig + (size_t)m * dig_stride;
+    if (COMPACT) {                            // k = k1 + lambda k2: rows 0..7 from |k1|, rows 8..15 from |k2| (entries of phi(P), see k_scatter)
+        const glv_t g = glv_decompose<C>(s);
+        recode_half(g.k1, g.neg1, d + i, n);
+        recode_half(g.k2, g.neg2, d + (size_t)NWIN_COMPACT * n + i, n);
+        return;
+    }
     uint32_t carry = 0;
 #pragma unroll
     for (int w = 0; w < NWIN; ++w) {
@@ -349,6 +376,14 @@ __global__ void SRS_KERNEL_BOUNDS(1024, 1)
 // their traffic costs.  Now a workgroup sorts a sub-tile of entries by segment (bucket) inside LDS and copies it out in index
 // order: consecutive lanes store consecutive addresses of a run.
 constexpr uint32_t GRP_PER = 16, GRP_SUB = SORT_THREADS * GRP_PER;      // digit slots per thread / per sub-tile of k_group
+// payload of digit row w, less the scalar's index: the table entry of window w -- for a compact key the entry of window w & 7, marked
+// as phi of it for the rows of k2
+template <bool COMPACT>
+__device__ __forceinline__ uint32_t payload_base(uint32_t w, uint32_t table_stride, uint32_t base) {
+    if (COMPACT) return ((w & (NWIN_COMPACT - 1)) * table_stride + base) | (w >= NWIN_COMPACT ? PAY_ENDO : 0u);
+    return w * table_stride + base;
+}
+template <bool COMPACT>
 __global__ void SRS_KERNEL_BOUNDS(SORT_THREADS, 1)
     k_group(const uint16_t *__restrict__ dig, size_t dig_stride, BatchDesc bd, const uint32_t *__restrict__ tile_hist,
             uint16_t *__restrict__ gkey, uint32_t *__restrict__ gpay, size_t g_stride, uint32_t table_stride, uint32_t SORT_TILE,
@@ -378,7 +413,7 @@ __global__ void SRS_KERNEL_BOUNDS(SORT_THREADS, 1)
     const uint16_t *d = dig + (size_t)m * dig_stride + (size_t)w * n;
     uint16_t *ok = gkey + (size_t)m * g_stride;
     uint32_t *op = gpay + (size_t)m * g_stride;
-    const uint32_t pay0 = w * table_stride + bd.base[m];
+    const uint32_t pay0 = payload_base<COMPACT>(w, table_stride, bd.base[m]);
     for (uint32_t sub = lo; sub < hi; sub += GRP_SUB) {                 // workgroup-uniform
         for (uint32_t sgm = tid; sgm < SEG; sgm += blockDim.x) cnt[sgm] = 0;
         __syncthreads();
@@ -504,6 +539,7 @@ __global__ void SRS_KERNEL_BOUNDS(SORT_THREADS, 2)
 #ifndef SCATTER_RES_INFLIGHT
 #define SCATTER_RES_INFLIGHT 4
 #endif
+template <bool COMPACT>
 __global__ void SRS_KERNEL_BOUNDS(SORT_THREADS, 1)
     k_scatter(const uint16_t *__restrict__ dig, size_t dig_stride, BatchDesc bd,
               uint32_t *__restrict__ cursor /* [batch][NBUCKET] */, uint32_t *__restrict__ sorted,
@@ -531,10 +567,11 @@ __global__ void SRS_KERNEL_BOUNDS(SORT_THREADS, 1)
     }
     __syncthreads();
     uint32_t *out = sorted + (size_t)m * sorted_stride;
+    const uint32_t pay0 = payload_base<COMPACT>(w, table_stride, bd.base[m]);
     for_each_digit(d, lo, hi, [&](uint32_t i, uint32_t code) {
         if (code != 0xFFFFu) {
             uint32_t pos = atomicAdd(&h[code & 0x7FFFu], 1u);
-            out[pos] = (w * table_stride + bd.base[m] + i) | ((code & 0x8000u) << 16);
+            out[pos] = (pay0 + i) | ((code & 0x8000u) << 16);
         }
     });
 }
@@ -1236,7 +1273,29 @@ __global__ void SRS_KERNEL_BOUNDS(256, 1)
 // r06: the loop runs the addition WITHOUT its exceptional cases (Ec29::madd_signed_fast: no identity tests, no branch, no doubling
 // path in the loop body); a chain that met one -- an identity entry of a degenerate key, a partial sum that cancelled, an entry equal to
 // the running sum -- is detected by a sticky flag and recomputed from its start with the complete formulas.
-template <class C>
+// COMPACT (compact keys, msm.h): bit 30 of an entry says that its point is phi(T[index]) = (beta x, y): the gathered x is multiplied by
+// beta.  The product does not depend on the running sum, so it sits beside the chain.  It is a per-lane BRANCH; the alternative, an
+// unconditional product with beta-or-one, measured within 3 % either way on a resident 2^24 MSM (uniform scalars: branch 22.4 ms, select
+// 22.6; 55 % zeros: branch 11.2-11.3, select 10.95; profiles/compact_key_ab.txt) -- the branch keeps 130 / 131 VGPRs against 134 / 129 and
+// lets a wavefront whose parts hold no flagged entry (scalars below 2^64 have k2 = 0) skip the product.
+// A table identity (0, 0) stays (0, 0) exactly -- the product of 0 is 0 --, so the exceptional-case tests of the chain hold unchanged.
+template <class C, bool COMPACT>
+__device__ __forceinline__ aff29_t load_entry(const affine_t &p, uint32_t v) {
+    aff29_t q = Ec29<C>::load_raw(p);
+    if (COMPACT) {
+        if (v & PAY_ENDO) {
+            f29_t beta;
+#pragma unroll
+            for (int i = 0; i < 9; ++i) beta.v[i] = GlvConsts<C::ID>::beta29(i);
+            q.x = Ec29<C>::F::mul(q.x, beta);        // < 2P norm: within the bounds of every use of a table x (curve29.cuh)
+        }
+    }
+    return q;
+}
+template <bool COMPACT>
+__device__ __forceinline__ uint32_t entry_index(uint32_t v) { return v & (COMPACT ? PAY_ENDO - 1u : 0x7FFFFFFFu); }
+
+template <class C, bool COMPACT>
 __device__ __forceinline__ xyzz29_t accumulate_part(const uint32_t *__restrict__ src, uint32_t s, uint32_t e, const affine_t *__restrict__ table,
                                                     const xyzz_t *__restrict__ init) {
     using E29 = Ec29<C>;
@@ -1246,7 +1305,7 @@ __device__ __forceinline__ xyzz29_t accumulate_part(const uint32_t *__restrict__
     {
         uint32_t v = src[s];
         uint32_t vn = s + 1 < e ? src[s + 1] : 0u;
-        affine_t p = table[v & 0x7FFFFFFFu];
+        affine_t p = table[entry_index<COMPACT>(v)];
         uint32_t j = s;
         if (init) {
             acc = E29::unpack(*init);
@@ -1254,10 +1313,10 @@ __device__ __forceinline__ xyzz29_t accumulate_part(const uint32_t *__restrict__
             affine_t pn = p;
             uint32_t vnn = 0;
             if (s + 1 < e) {
-                pn = table[vn & 0x7FFFFFFFu];
+                pn = table[entry_index<COMPACT>(vn)];
                 if (s + 2 < e) vnn = src[s + 2];
             }
-            const aff29_t q = E29::load_raw(p);
+            const aff29_t q = load_entry<C, COMPACT>(p, v);
             acc.x = q.x;
             acc.y = (v >> 31) ? F::normalize(F::template neg_lazy<1, 0>(q.y)) : q.y;      // P - y  (y != 0 unless Q = O: flagged)
             acc.zz = E29::one();
@@ -1272,10 +1331,10 @@ __device__ __forceinline__ xyzz29_t accumulate_part(const uint32_t *__restrict__
             uint32_t vnn = 0;
             affine_t pn = p;
             if (j + 1 < e) {
-                pn = table[vn & 0x7FFFFFFFu];
+                pn = table[entry_index<COMPACT>(vn)];
                 if (j + 2 < e) vnn = src[j + 2];
             }
-            acc = E29::madd_signed_fast(acc, E29::load_raw(p), (v >> 31) != 0, exc);
+            acc = E29::madd_signed_fast(acc, load_entry<C, COMPACT>(p, v), (v >> 31) != 0, exc);
             v = vn;
             vn = vnn;
             p = pn;
@@ -1286,17 +1345,17 @@ __device__ __forceinline__ xyzz29_t accumulate_part(const uint32_t *__restrict__
 #pragma unroll 1
         for (uint32_t j = s; j < e; ++j) {
             const uint32_t v = src[j];
-            acc = E29::madd_signed(acc, E29::load_raw(table[v & 0x7FFFFFFFu]), (v >> 31) != 0);
+            acc = E29::madd_signed(acc, load_entry<C, COMPACT>(table[entry_index<COMPACT>(v)], v), (v >> 31) != 0);
         }
     }
     return acc;
 }
 
-template <class C>
-__global__ void SRS_KERNEL_BOUNDS(ACC_THREADS, 1)
-    k_accum0(const uint32_t *__restrict__ sorted, size_t sorted_stride, const uint32_t *__restrict__ plan,
-             size_t plan_stride, const uint16_t *__restrict__ tb, size_t tb_stride, const affine_t *__restrict__ table,
-             xyzz_t *__restrict__ parts, size_t parts_stride, uint32_t l0, const Link *__restrict__ link) {
+template <class C, bool COMPACT>
+__device__ __forceinline__ void accum0_thread(const uint32_t *__restrict__ sorted, size_t sorted_stride, const uint32_t *__restrict__ plan,
+                                              size_t plan_stride, const uint16_t *__restrict__ tb, size_t tb_stride,
+                                              const affine_t *__restrict__ table, xyzz_t *__restrict__ parts, size_t parts_stride, uint32_t l0,
+                                              const Link *__restrict__ link) {
     uint32_t m = blockIdx.y;
     uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     size_t slot;                                   // index of this thread's part (and map entry)
@@ -1319,8 +1378,23 @@ __global__ void SRS_KERNEL_BOUNDS(ACC_THREADS, 1)
     const uint32_t *src = link ? sorted : sorted + (size_t)m * sorted_stride;
     // the additions run on the 9 x 29-bit limb form (curve29.cuh); the table is stored in its Montgomery form
     using E29 = Ec29<C>;
-    const xyzz29_t acc = s < e ? accumulate_part<C>(src, s, e, table, nullptr) : E29::identity();
+    const xyzz29_t acc = s < e ? accumulate_part<C, COMPACT>(src, s, e, table, nullptr) : E29::identity();
     parts[slot] = E29::pack(acc);                                // canonical R'-form: the later levels stay on the 29-bit multiplier
+}
+template <class C>
+__global__ void SRS_KERNEL_BOUNDS(ACC_THREADS, 1)
+    k_accum0(const uint32_t *__restrict__ sorted, size_t sorted_stride, const uint32_t *__restrict__ plan,
+             size_t plan_stride, const uint16_t *__restrict__ tb, size_t tb_stride, const affine_t *__restrict__ table,
+             xyzz_t *__restrict__ parts, size_t parts_stride, uint32_t l0, const Link *__restrict__ link) {
+    accum0_thread<C, false>(sorted, sorted_stride, plan, plan_stride, tb, tb_stride, table, parts, parts_stride, l0, link);
+}
+// the same for a compact key (entries flagged PAY_ENDO): a kernel of its own, so that the one full keys launch is compiled as before
+template <class C>
+__global__ void SRS_KERNEL_BOUNDS(ACC_THREADS, 1)
+    k_accum0c(const uint32_t *__restrict__ sorted, size_t sorted_stride, const uint32_t *__restrict__ plan,
+              size_t plan_stride, const uint16_t *__restrict__ tb, size_t tb_stride, const affine_t *__restrict__ table,
+              xyzz_t *__restrict__ parts, size_t parts_stride, uint32_t l0, const Link *__restrict__ link) {
+    accum0_thread<C, true>(sorted, sorted_stride, plan, plan_stride, tb, tb_stride, table, parts, parts_stride, l0, link);
 }
 
 // 64-lane exchange of an XYZZ point
@@ -1430,11 +1504,11 @@ __global__ void SRS_KERNEL_BOUNDS(FINAL_THREADS, 1)
 //                -- nothing is left for later levels to combine, whatever the number of sets a commit is cut into;
 //   p >= S - 1 : a hot bucket (more entries than S - 1 parts hold): a fresh partial sum into `ovf`, combined by k_accum1 / k_ovf_final.
 // grid = (ceil(cap / ACC_THREADS), batch)
-template <class C>
-__global__ void SRS_KERNEL_BOUNDS(ACC_THREADS, 1)
-    k_accum0s(const uint32_t *__restrict__ sorted, size_t sorted_stride, const uint32_t *__restrict__ plan, size_t plan_stride, uint32_t arr,
-              const uint16_t *__restrict__ tb, size_t tb_stride, const affine_t *__restrict__ table, xyzz_t *__restrict__ slots, uint32_t S,
-              const uint8_t *__restrict__ used_prev, int first, xyzz_t *__restrict__ ovf, size_t ovf_stride) {
+template <class C, bool COMPACT>
+__device__ __forceinline__ void accum0s_thread(const uint32_t *__restrict__ sorted, size_t sorted_stride, const uint32_t *__restrict__ plan,
+                                               size_t plan_stride, uint32_t arr, const uint16_t *__restrict__ tb, size_t tb_stride,
+                                               const affine_t *__restrict__ table, xyzz_t *__restrict__ slots, uint32_t S,
+                                               const uint8_t *__restrict__ used_prev, int first, xyzz_t *__restrict__ ovf, size_t ovf_stride) {
     const uint32_t m = blockIdx.y;
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t *off = plan + (size_t)m * plan_stride;
@@ -1453,7 +1527,21 @@ __global__ void SRS_KERNEL_BOUNDS(ACC_THREADS, 1)
     xyzz_t *slot = regular ? slots + ((size_t)m * NBUCKET + b) * S + part : ovf + (size_t)m * ovf_stride + tpo[b] + (part - (S - 1));
     // a part is never empty (s < e); the slot's running sum is the start value when the slot holds one
     const bool resume = regular && !first && part < (uint32_t)used_prev[(size_t)m * NBUCKET + b];
-    *slot = E29::pack(accumulate_part<C>(src, s, e, table, resume ? slot : nullptr));
+    *slot = E29::pack(accumulate_part<C, COMPACT>(src, s, e, table, resume ? slot : nullptr));
+}
+template <class C>
+__global__ void SRS_KERNEL_BOUNDS(ACC_THREADS, 1)
+    k_accum0s(const uint32_t *__restrict__ sorted, size_t sorted_stride, const uint32_t *__restrict__ plan, size_t plan_stride, uint32_t arr,
+              const uint16_t *__restrict__ tb, size_t tb_stride, const affine_t *__restrict__ table, xyzz_t *__restrict__ slots, uint32_t S,
+              const uint8_t *__restrict__ used_prev, int first, xyzz_t *__restrict__ ovf, size_t ovf_stride) {
+    accum0s_thread<C, false>(sorted, sorted_stride, plan, plan_stride, arr, tb, tb_stride, table, slots, S, used_prev, first, ovf, ovf_stride);
+}
+template <class C>
+__global__ void SRS_KERNEL_BOUNDS(ACC_THREADS, 1)
+    k_accum0sc(const uint32_t *__restrict__ sorted, size_t sorted_stride, const uint32_t *__restrict__ plan, size_t plan_stride, uint32_t arr,
+               const uint16_t *__restrict__ tb, size_t tb_stride, const affine_t *__restrict__ table, xyzz_t *__restrict__ slots, uint32_t S,
+               const uint8_t *__restrict__ used_prev, int first, xyzz_t *__restrict__ ovf, size_t ovf_stride) {
+    accum0s_thread<C, true>(sorted, sorted_stride, plan, plan_stride, arr, tb, tb_stride, table, slots, S, used_prev, first, ovf, ovf_stride);
 }
 
 // the wave-level pass of the overflow parts: one wavefront per bucket sums what the overflow levels left of it and adds the sum into the
@@ -1717,8 +1805,8 @@ static void build_table_t(Key &k, hipStream_t stream) {
     xyzz_t *tmp = nullptr;
     SRS_HIP_CHECK(hipMalloc((void **)&tmp, (size_t)n * sizeof(xyzz_t)));
     // the second table is an optimisation (+81 % key memory): a device that cannot hold it keeps the 16-bit windows for everything
-    // (use_wide() is false without table_w; srs_ck_has_wide_table tells)
-    if (wants_wide_table(n) && hipMalloc((void **)&k.table_w, (size_t)n * NWIN_W * sizeof(affine_t)) != hipSuccess) {
+    // (use_wide() is false without table_w; srs_ck_has_wide_table tells).  A compact key is the memory-saving form: it never has one.
+    if (!k.compact && wants_wide_table(n) && hipMalloc((void **)&k.table_w, (size_t)n * NWIN_W * sizeof(affine_t)) != hipSuccess) {
         (void)hipGetLastError();
         k.table_w = nullptr;
     }
@@ -1728,8 +1816,9 @@ static void build_table_t(Key &k, hipStream_t stream) {
         const size_t total_w = (size_t)n * NWIN_W;
         SRS_LAUNCH((k_table_form<C>), (ceil_div(total_w, 256)), (256), 0, stream, k.table_w, total_w);
     }
-    expand_windows<C>(k.table, n, NWIN, WBITS, tmp, stream);
-    const size_t total = (size_t)n * NWIN;
+    const int nwin = k.compact ? NWIN_COMPACT : NWIN;
+    expand_windows<C>(k.table, n, nwin, WBITS, tmp, stream);
+    const size_t total = (size_t)n * nwin;
     SRS_LAUNCH((k_table_form<C>), (ceil_div(total, 256)), (256), 0, stream, k.table, total);
     SRS_HIP_CHECK(hipStreamSynchronize(stream));
     SRS_HIP_CHECK(hipFree(tmp));
@@ -1772,6 +1861,21 @@ void read_bases(const Key &k, affine_t *out_dev, hipStream_t stream) {
 
 void build_table(Key &k, hipStream_t stream) {
     if (k.curve == 0) build_table_t<Bn256>(k, stream); else build_table_t<Grumpkin>(k, stream);
+}
+
+int choose_windows(Key &k) {
+    k.compact = tuning::get_or(tuning::MSM_COMPACT, 0) == 1;
+    // the largest index, NWIN_COMPACT * len - 1, must lie below the endomorphism flag of an entry.  A guard: every creation entry already
+    // refuses keys above 2^27 bases (capi.hip), and 8 x 2^27 = 2^30 still fits, so this cannot fire while that limit stands.
+    if (k.compact && (uint64_t)NWIN_COMPACT * k.len > PAY_ENDO) {
+        set_error("compact key (msm_compact = 1): 8 x " + std::to_string(k.len) + " table entries do not fit below the endomorphism flag (2^30)");
+        throw DeviceError{4};      // SRS_ERR_INVALID
+    }
+    return k.compact ? NWIN_COMPACT : NWIN;
+}
+size_t table_bytes(const Key &k) {
+    if (!k.table) return 0;
+    return k.len * sizeof(affine_t) * ((k.compact ? NWIN_COMPACT : NWIN) + (k.table_w ? NWIN_W : 0));
 }
 
 // ---- host driver: three flows (16-bit windows with levels / in slot mode, wide windows) over shared stages -----------------------
@@ -2030,14 +2134,18 @@ static void sort_front(const Key &k, const SetShape &h, const SetBufs &b, const 
     }
     const uint32_t s_rank = k.compact_scalars ? 0u : k.rank, s_world = k.compact_scalars ? 1u : k.world;
     const size_t M = (size_t)h.M;
-    SRS_LAUNCH((k_digits<C>), (ceil_div(n_max, 256), batch), (256), 0, stream, bd, b.dig, M, is_mont, s_rank, s_world, b.count,
+    // a compact key differs in three kernels of this stage -- the split digits and the payload line of either scatter -- and in level 0
+    const auto digits = k.compact ? &k_digits<C, true> : &k_digits<C, false>;
+    const auto group = k.compact ? &k_group<true> : &k_group<false>;
+    const auto scatter = k.compact ? &k_scatter<true> : &k_scatter<false>;
+    SRS_LAUNCH(digits, (ceil_div(n_max, 256), batch), (256), 0, stream, bd, b.dig, M, is_mont, s_rank, s_world, b.count,
                (uint32_t)(NBUCKET * batch));
     SRS_LAUNCH(k_hist, (h.tiles, NWIN, batch), (SORT_THREADS), 0, stream, (const uint16_t *)b.dig, M, bd, b.count, h.tile, b.tile_hist);
     launch_plan();
     if (h.two_pass) {
         const uint32_t T1 = h.tiles * NWIN;
         SRS_LAUNCH(k_scan_seg, (SEG, batch), (1024), 0, stream, b.tile_hist, T1, (const uint32_t *)b.plan, h.plan_stride);
-        SRS_LAUNCH(k_group, (h.tiles, NWIN, batch), (SORT_THREADS), 0, stream, (const uint16_t *)b.dig, M, bd, (const uint32_t *)b.tile_hist,
+        SRS_LAUNCH(group, (h.tiles, NWIN, batch), (SORT_THREADS), 0, stream, (const uint16_t *)b.dig, M, bd, (const uint32_t *)b.tile_hist,
                    b.gkey, b.gpay, M, (uint32_t)k.len, h.tile, group_maps ? (const uint32_t *)b.plan : nullptr,
                    group_maps ? h.plan_stride : (size_t)0, group_maps ? b.tb : nullptr, group_maps ? (size_t)h.cap0 : (size_t)0,
                    group_maps ? arr : 0u);
@@ -2045,7 +2153,7 @@ static void sort_front(const Key &k, const SetShape &h, const SetBufs &b, const 
         SRS_LAUNCH(k_scatter2, (8 * ceil_div(ceil_div(M, SORT_TILE2), 8), batch), (SORT_THREADS), 0, stream, (const uint16_t *)b.gkey,
                    (const uint32_t *)b.gpay, M, (const uint32_t *)b.plan, h.plan_stride, b.cursor, b.sorted, M, (uint32_t)SORT_TILE2);
     } else {
-        SRS_LAUNCH(k_scatter, (h.tiles, NWIN, batch), (SORT_THREADS), 0, stream, (const uint16_t *)b.dig, M, bd, b.cursor, b.sorted, M,
+        SRS_LAUNCH(scatter, (h.tiles, NWIN, batch), (SORT_THREADS), 0, stream, (const uint16_t *)b.dig, M, bd, b.cursor, b.sorted, M,
                    (uint32_t)k.len, h.tile);
     }
     if (!(h.two_pass && group_maps))
@@ -2111,7 +2219,8 @@ static bool enqueue_t(Key &k, const fe_t *const *scalars_dev, const uint32_t *n_
     }, false, 1u);
     const Parts p{b.plan, h.plan_stride, b.ping, (size_t)h.cap0, b.pong, (size_t)h.cap1, nullptr};
     const uint64_t units = std::accumulate(n_host, n_host + batch, (uint64_t)0);
-    SRS_LAUNCH_TIMED("msm_accum0", units, (k_accum0<C>), (ceil_div(h.cap0, ACC_THREADS), batch), (ACC_THREADS), 0, stream,
+    const auto accum0 = k.compact ? &k_accum0c<C> : &k_accum0<C>;
+    SRS_LAUNCH_TIMED("msm_accum0", units, accum0, (ceil_div(h.cap0, ACC_THREADS), batch), (ACC_THREADS), 0, stream,
                      (const uint32_t *)b.sorted, (size_t)h.M, p.plan, p.plan_stride, (const uint16_t *)b.tb, p.stride0,
                      (const affine_t *)k.table, p.ping, p.stride0, 1u << h.l0_log, p.link);
     accum_levels<C>(p, h, NBUCKET + 1, batch, stream);
@@ -2188,7 +2297,8 @@ static bool enqueue_slots_t(Key &k, const fe_t *const *scalars_dev, const uint32
     }, true, arr);
     const Parts p{b.plan, h.plan_stride, b.ping, (size_t)h.cap0, b.pong, (size_t)h.cap1, nullptr};
     const uint64_t units = std::accumulate(n_host, n_host + batch, (uint64_t)0);
-    SRS_LAUNCH_TIMED("msm_accum0", units, (k_accum0s<C>), (ceil_div(h.cap0, ACC_THREADS), batch), (ACC_THREADS), 0, stream,
+    const auto accum0s = k.compact ? &k_accum0sc<C> : &k_accum0s<C>;
+    SRS_LAUNCH_TIMED("msm_accum0", units, accum0s, (ceil_div(h.cap0, ACC_THREADS), batch), (ACC_THREADS), 0, stream,
                      (const uint32_t *)b.sorted, (size_t)h.M, p.plan, p.plan_stride, arr, (const uint16_t *)b.tb, p.stride0,
                      (const affine_t *)k.table, k.slots, S, used_prev, first ? 1 : 0, p.ping, p.stride0);
     if (k.commit_ovf) {                      // hot buckets expected: the parts beyond the slots go through the level kernels into slot S - 1

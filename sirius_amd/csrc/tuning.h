@@ -3,7 +3,7 @@
 // Every tunable selects among code paths that the library takes BY DEFAULT for some input size (single- vs two-pass sort, the
 // part length of level 0, 16- vs 20-bit windows, the number of chunks of a streamed commit, ...), or moves the size threshold
 // between them; none changes a result.  They exist so that a test can run a large-input path on an input small enough for the
-// CPU oracle to check, and so that a deployer can trade memory for speed (msm_wide).  Variants that were measured slower and
+// CPU oracle to check, and so that a deployer can trade memory for speed (msm_wide) or speed for memory (msm_compact).  Variants that were measured slower and
 // are no default anywhere are not selectable: they were removed from the library (records: profiles/*_ab_*.txt).
 #pragma once
 #include <cstdint>
@@ -25,6 +25,7 @@ enum Id : int {
     PG_G_FFT,           // 1: compute_G on the roots of unity + ifft (the path of L >= 2 incoming traces) instead of integer points
     JIT_ALWAYS,         // 1: run-time compile the sweep kernels below k = 14 as well
     NO_JIT,             // 1: never call hiprtc (also: environment SRS_NO_JIT, for deployments without the hiprtc library)
+    MSM_COMPACT,        // 0 full key (16 windows) | 1 compact key: 8 windows + the curve endomorphism (half the key's HBM, no 20-bit table); read when a key is created
     N_TUNABLES
 };
 
