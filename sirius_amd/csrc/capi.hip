@@ -267,16 +267,6 @@ int guarded(Fn &&fn) {
 bool valid_curve(int c) { return c == SRS_CURVE_BN256 || c == SRS_CURVE_GRUMPKIN; }
 bool valid_field(int f) { return f == SRS_FIELD_FR || f == SRS_FIELD_FQ; }
 
-size_t shard_count(size_t n, uint32_t rank, uint32_t world) {
-    if (world == 1) return n;
-    const size_t S = (size_t)1 << msm::STRIPE_LOG;
-    size_t full = n >> msm::STRIPE_LOG, rem = n & (S - 1);
-    size_t cnt = (full / world) * S;
-    if (rank < full % world) cnt += S;
-    if (rank == full % world) cnt += rem;
-    return cnt;
-}
-
 // XYZZ -> affine for a batch with ONE field inversion (Montgomery's trick); identities pass through
 template <class C>
 void to_affine_batch_t(const xyzz_t *in, affine_t *out, size_t n) {
@@ -328,27 +318,30 @@ int physical_device_count() {
     return n;
 }
 
-// copies the block-cyclic stripes of shard `d` (stripe s with s % world == d) of src[0 .. n) compactly to dst (a buffer on
-// the shard's device); src is host memory or memory of the process's device.  One strided copy for the whole stripes
-// plus one for the tail.  Returns the number of elements copied (= shard_count(n, d, world)).
-size_t copy_stripes(fe_t *dst, const fe_t *src, size_t n, uint32_t d, uint32_t world, bool src_is_device, hipStream_t st) {
-    const size_t S = (size_t)1 << msm::STRIPE_LOG;
-    const hipMemcpyKind kind = src_is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    if (world == 1) {
-        if (n) SRS_HIP_CHECK(hipMemcpyAsync(dst, src, n * sizeof(fe_t), kind, st));
-        return n;
+// The one place stripes turn into HIP traffic: the elements of [a, b) that `sp` owns are copied from `src` (element g of the vector is
+// src[g - src_off]), or zeroed when src == nullptr, to dst -- COMPACT: at their local offsets (a buffer of the shard's own elements), else in
+// place, at their global offsets.  Per run of Stripes::runs one operation: a partial stripe is a plain copy / memset, the whole stripes are
+// ONE strided 2-D copy / memset with pitch world * 2^STRIPE_LOG elements.  -> elements handled (= sp.count(a, b))
+size_t stripe_copy(Stripes sp, size_t a, size_t b, fe_t *dst, bool compact, const fe_t *src, size_t src_off, hipMemcpyKind kind, hipStream_t st) {
+    const size_t pitch = (size_t)sp.world * Stripes::S * sizeof(fe_t);
+    Run run[3];
+    const int n = sp.runs(a, b, run);
+    size_t done = 0;
+    for (int i = 0; i < n; ++i) {
+        const Run &r = run[i];
+        fe_t *d = dst + (compact ? r.local : r.global);
+        const fe_t *s = src ? src + (r.global - src_off) : nullptr;
+        const size_t bytes = r.width * sizeof(fe_t), dpitch = compact ? Stripes::S * sizeof(fe_t) : pitch;
+        if (r.rows == 1) {
+            if (s) SRS_HIP_CHECK(hipMemcpyAsync(d, s, bytes, kind, st));
+            else SRS_HIP_CHECK(hipMemsetAsync(d, 0, bytes, st));
+        } else {
+            if (s) SRS_HIP_CHECK(hipMemcpy2DAsync(d, dpitch, s, pitch, bytes, r.rows, kind, st));
+            else SRS_HIP_CHECK(hipMemset2DAsync(d, dpitch, 0, bytes, r.rows, st));
+        }
+        done += r.width * r.rows;
     }
-    const size_t full = n >> msm::STRIPE_LOG, rem = n & (S - 1);
-    const size_t mine = full / world + (d < full % world ? 1 : 0);          // whole stripes of this shard
-    if (mine)
-        SRS_HIP_CHECK(hipMemcpy2DAsync(dst, S * sizeof(fe_t), src + (size_t)d * S, (size_t)world * S * sizeof(fe_t),
-                                       S * sizeof(fe_t), mine, kind, st));
-    size_t cnt = mine * S;
-    if (rem && d == full % world) {
-        SRS_HIP_CHECK(hipMemcpyAsync(dst + cnt, src + full * S, rem * sizeof(fe_t), kind, st));
-        cnt += rem;
-    }
-    return cnt;
+    return done;
 }
 
 template <class C>
@@ -373,7 +366,7 @@ int multi_commit(srs_ck *ck, const srs_fe *const *scalars, const size_t *n, size
             size_t total = 256;
             std::vector<uint32_t> nloc(batch);
             for (size_t m = 0; m < batch; ++m) {
-                nloc[m] = (uint32_t)shard_count(n[m], d, world);
+                nloc[m] = (uint32_t)Stripes{d, world}.count(n[m]);
                 total += Arena::pad(((size_t)nloc[m] + 1) * sizeof(fe_t));
             }
             sh->staging.reserve(total);
@@ -382,7 +375,8 @@ int multi_commit(srs_ck *ck, const srs_fe *const *scalars, const size_t *n, size
             std::vector<const fe_t *> dptr(batch);
             for (size_t m = 0; m < batch; ++m) {
                 fe_t *dst = sh->staging.take<fe_t>((size_t)nloc[m] + 1);
-                copy_stripes(dst, reinterpret_cast<const fe_t *>(scalars[m]), n[m], d, world, space == SRS_SPACE_DEVICE, sh->stream);
+                stripe_copy(Stripes{d, world}, 0, n[m], dst, true, reinterpret_cast<const fe_t *>(scalars[m]), 0,
+                            space == SRS_SPACE_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, sh->stream);
                 dptr[m] = dst;
             }
             msm::run(sh->key, dptr.data(), nloc.data(), (uint32_t)batch, repr == SRS_REPR_MONT, sh->stream, parts[d].data());
@@ -447,7 +441,7 @@ int create_multi(int curve, size_t len, int n_devices, Fill fill, srs_ck **out) 
             sh->key.global_len = len;
             sh->key.rank = d;
             sh->key.world = world;
-            sh->key.len = shard_count(len, d, world);
+            sh->key.len = Stripes{d, world}.count(len);
             sh->key.compact_scalars = true;                    // the shard is handed ITS scalars, already gathered
             SRS_HIP_CHECK(hipSetDevice(sh->device));
             if (sh->device != home) {        // stripes of device-resident scalars come, and streamed stripes leave, by peer copies: they need the access
@@ -643,24 +637,16 @@ int srs_ck_create_sharded(int curve, const srs_affine *bases, size_t len, int sp
         ck->key.global_len = len;
         ck->key.rank = rank;
         ck->key.world = world;
-        ck->key.len = shard_count(len, rank, world);
+        ck->key.len = Stripes{rank, world}.count(len);
         const size_t n = ck->key.len;
         try {
             const size_t windows = msm::choose_windows(ck->key);      // the key's form, decided for an empty key or shard too
             if (n) {
                 SRS_HIP_CHECK(hipMalloc((void **)&ck->key.table, n * windows * sizeof(affine_t)));
                 const hipMemcpyKind kind = space == SRS_SPACE_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-                if (world == 1) {
-                    SRS_HIP_CHECK(hipMemcpy(ck->key.table, bases, n * sizeof(affine_t), kind));
-                } else {
-                    const size_t S = (size_t)1 << msm::STRIPE_LOG;
-                    size_t local = 0;
-                    for (size_t s = rank; s * S < len; s += world) {
-                        size_t cnt = std::min(S, len - s * S);
-                        SRS_HIP_CHECK(hipMemcpy(ck->key.table + local, bases + s * S, cnt * sizeof(affine_t), kind));
-                        local += cnt;
-                    }
-                }
+                Stripes{rank, world}.each_piece(0, len, [&](size_t g, size_t l, size_t cnt) {       // one copy per stripe (world == 1: one in all)
+                    SRS_HIP_CHECK(hipMemcpy(ck->key.table + l, bases + g, cnt * sizeof(affine_t), kind));
+                });
                 msm::build_table(ck->key, nullptr);
             }
         } catch (...) {
@@ -683,7 +669,7 @@ int srs_ck_setup_synthetic(int curve, size_t len, uint64_t seed, uint32_t rank, 
         ck->key.global_len = len;
         ck->key.rank = rank;
         ck->key.world = world;
-        ck->key.len = shard_count(len, rank, world);
+        ck->key.len = Stripes{rank, world}.count(len);
         try {
             const size_t windows = msm::choose_windows(ck->key);
             if (ck->key.len) {
@@ -722,19 +708,15 @@ int srs_ck_get_bases(const srs_ck *ck, srs_affine *out) {
     if (rc) return rc;
     if (!ck->shards.empty()) {           // multi-device key: the whole key, stripes gathered from the shards
         return guarded([&]() -> int {
-            const size_t S = (size_t)1 << msm::STRIPE_LOG, len = ck->key.global_len;
             const uint32_t world = (uint32_t)ck->shards.size();
             for (uint32_t d = 0; d < world; ++d) {
                 CkShard *sh = ck->shards[d].get();
                 std::vector<srs_affine> loc(sh->key.len);
                 SRS_HIP_CHECK(hipSetDevice(sh->device));
                 read_shard_bases(sh->key, sh->stream, loc.data());
-                size_t at = 0;
-                for (size_t st = d; st * S < len; st += world) {
-                    size_t cnt = std::min(S, len - st * S);
-                    std::memcpy(out + st * S, loc.data() + at, cnt * sizeof(srs_affine));
-                    at += cnt;
-                }
+                Stripes{d, world}.each_piece(0, ck->key.global_len, [&](size_t g, size_t l, size_t cnt) {
+                    std::memcpy(out + g, loc.data() + l, cnt * sizeof(srs_affine));
+                });
             }
             return ensure_device();
         });
@@ -827,14 +809,10 @@ int srs_ck_create_multi(int curve, const srs_affine *bases, size_t len, int spac
     if (rc) return rc;
     return guarded([&]() -> int {
         return create_multi(curve, len, n_devices, [&](CkShard &sh) {
-            const size_t S = (size_t)1 << msm::STRIPE_LOG;
             const hipMemcpyKind kind = space == SRS_SPACE_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-            size_t local = 0;
-            for (size_t st = sh.key.rank; st * S < len; st += sh.key.world) {
-                size_t cnt = std::min(S, len - st * S);
-                SRS_HIP_CHECK(hipMemcpyAsync(sh.key.table + local, bases + st * S, cnt * sizeof(affine_t), kind, sh.stream));
-                local += cnt;
-            }
+            Stripes{sh.key.rank, sh.key.world}.each_piece(0, len, [&](size_t g, size_t l, size_t cnt) {        // one copy per stripe
+                SRS_HIP_CHECK(hipMemcpyAsync(sh.key.table + l, bases + g, cnt * sizeof(affine_t), kind, sh.stream));
+            });
         }, out);
     });
 }
@@ -991,7 +969,7 @@ int srs_commit_batch(srs_ck *ck, const srs_fe *const *scalars, const size_t *n, 
         const uint32_t world = ck->key.world, rank = ck->key.rank;
         std::vector<uint32_t> nloc(batch);
         std::vector<const fe_t *> dptr(batch);
-        for (size_t m = 0; m < batch; ++m) nloc[m] = (uint32_t)shard_count(n[m], rank, world);
+        for (size_t m = 0; m < batch; ++m) nloc[m] = (uint32_t)Stripes{rank, world}.count(n[m]);
         if (space == SRS_SPACE_DEVICE) {
             for (size_t m = 0; m < batch; ++m) dptr[m] = reinterpret_cast<const fe_t *>(scalars[m]);
         } else {
@@ -1039,70 +1017,20 @@ static bool host_is_pageable(const void *p) {
     return attr.type == hipMemoryTypeUnregistered;
 }
 
-// uploads dst[a, b) = pieces + zero padding, on stream `cs`
-void upload_range(fe_t *dst, const std::vector<Seg> &segs, size_t a, size_t b, hipStream_t cs) {
-    size_t at = a;
+// uploads the elements of dst[a, b) that `sp` owns -- pieces + zero padding up to the next piece / b -- to their global positions, on stream
+// `cs`: per piece and per stretch of padding the operations of stripe_copy (world == 1: one copy / one memset; a rank of a block-cyclic
+// sharding: the whole stripes as ONE strided copy / memset plus the partial stripes at either end, a dozen operations per chunk whatever
+// its size; pieces may start anywhere, stripes are global).  -> data elements copied
+size_t upload(fe_t *dst, const std::vector<Seg> &segs, size_t a, size_t b, Stripes sp, hipStream_t cs) {
+    size_t at = a, copied = 0;
     for (const Seg &sg : segs) {
         const size_t lo = std::max(a, sg.off), hi = std::min(b, sg.off + sg.len);
         if (lo >= hi) continue;
-        if (lo > at) SRS_HIP_CHECK(hipMemsetAsync(dst + at, 0, (lo - at) * sizeof(fe_t), cs));
-        SRS_HIP_CHECK(hipMemcpyAsync(dst + lo, sg.src + (lo - sg.off), (hi - lo) * sizeof(fe_t), hipMemcpyHostToDevice, cs));
+        stripe_copy(sp, at, lo, dst, false, nullptr, 0, hipMemcpyHostToDevice, cs);
+        copied += stripe_copy(sp, lo, hi, dst, false, sg.src, sg.off, hipMemcpyHostToDevice, cs);
         at = hi;
     }
-    if (b > at) SRS_HIP_CHECK(hipMemsetAsync(dst + at, 0, (b - at) * sizeof(fe_t), cs));
-}
-
-// The same for ONE RANK of a block-cyclic sharding: uploads rank R's stripes (2^STRIPE_LOG elements; stripe s belongs to rank s % W) of the global
-// range [a, b) of the concatenation -- pieces + zero padding up to the next piece / n -- to their global positions in dst.  Per piece and kind
-// (data / padding) the whole stripes are ONE strided copy (or strided memset), partial stripes at the ends of a piece one small operation
-// each: a dozen operations per chunk whatever its size.  Pieces may start anywhere (stripes are global).  -> data elements copied.
-size_t upload_stripes(fe_t *dst, const std::vector<Seg> &segs, size_t n, size_t a, size_t b, uint32_t R, uint32_t W, hipStream_t cs) {
-    const size_t SL = (size_t)1 << msm::STRIPE_LOG, pitch = (size_t)W * SL * sizeof(fe_t);
-    size_t copied = 0;
-    auto over = [&](size_t lo, size_t hi, const fe_t *src /* element at global offset lo, or nullptr: zeros */) {
-        lo = std::max(lo, a);
-        const size_t lo0 = lo;
-        hi = std::min(hi, b);
-        if (lo >= hi) return;
-        auto op1 = [&](size_t g, size_t len) {
-            if (src) { SRS_HIP_CHECK(hipMemcpyAsync(dst + g, src + (g - lo0), len * sizeof(fe_t), hipMemcpyHostToDevice, cs)); copied += len; }
-            else SRS_HIP_CHECK(hipMemsetAsync(dst + g, 0, len * sizeof(fe_t), cs));
-        };
-        size_t s_lo = lo / SL;
-        const size_t s_last = (hi - 1) / SL;
-        if (s_lo == s_last) {                              // inside one stripe
-            if (s_lo % W == R) op1(lo, hi - lo);
-            return;
-        }
-        if (lo % SL) {                                     // partial first stripe
-            if (s_lo % W == R) op1(lo, (s_lo + 1) * SL - lo);
-            ++s_lo;
-        }
-        const size_t full_end = hi / SL;                   // stripes [s_lo, full_end) are whole
-        if (hi % SL && full_end % W == R) op1(full_end * SL, hi - full_end * SL);          // partial last stripe
-        if (s_lo < full_end) {
-            const size_t s0 = s_lo + ((R + W - s_lo % W) % W);
-            if (s0 < full_end) {
-                const size_t rows = (full_end - s0 + W - 1) / W, g = s0 * SL;
-                if (src) {
-                    SRS_HIP_CHECK(hipMemcpy2DAsync(dst + g, pitch, src + (g - lo0), pitch, SL * sizeof(fe_t), rows, hipMemcpyHostToDevice, cs));
-                    copied += rows * SL;
-                } else {
-                    SRS_HIP_CHECK(hipMemset2DAsync(dst + g, pitch, 0, SL * sizeof(fe_t), rows, cs));
-                }
-            }
-        }
-    };
-    size_t at = 0;                                         // everything before the first piece is padding too
-    for (size_t k = 0; k < segs.size(); ++k) {
-        const Seg &sg = segs[k];
-        if (sg.off > at) over(at, sg.off, nullptr);
-        // (the data pointer handed to `over` must point at the element of global offset max(sg.off, a))
-        const size_t d_lo = std::max(sg.off, a);
-        if (sg.len && d_lo < sg.off + sg.len) over(sg.off, sg.off + sg.len, sg.src + (d_lo - sg.off));
-        at = std::max(at, sg.off + sg.len);
-    }
-    if (n > at) over(at, n, nullptr);
+    stripe_copy(sp, at, b, dst, false, nullptr, 0, hipMemcpyHostToDevice, cs);
     return copied;
 }
 
@@ -1110,7 +1038,7 @@ size_t upload_stripes(fe_t *dst, const std::vector<Seg> &segs, size_t n, size_t 
 // stream while the MSM of chunk j - 1 runs on the caller's stream; `cuts` = chunk boundaries (element offsets, first 0, last n)
 // A key sharded over processes (world > 1; chunk boundaries multiples of world * 2^10): every chunk brings up and accumulates only THIS rank's
 // block-cyclic stripes of its range -- the same overlap of upload and MSM, 1 / world of both per rank (r05: from any list of pieces, so the
-// column form streams too: upload_stripes).
+// column form streams too: upload).
 // The stream resources of whoever runs the commit -- a single-device key handle, or one shard of a multi-device key -- and, for a
 // shard, where its stripes are forwarded once they are in its HBM (the device copy the caller asked for lives on the process's device).
 struct StreamRes {
@@ -1131,11 +1059,10 @@ int commit_streamed_core(StreamRes ck_, const std::vector<Seg> &segs, size_t n, 
     StreamRes *ck = &ck_;
     HostTrace ht("commit_streamed");
     const size_t chunks = cut.size() - 1;
-    const uint32_t W = ck->key.world, R = ck->key.rank;
-    const size_t SL = (size_t)1 << msm::STRIPE_LOG;
-    auto local = [&](size_t a, size_t b) { return shard_count(b, R, W) - shard_count(a, R, W); };     // this rank's elements of [a, b)
+    const uint32_t W = ck->key.world;
+    const Stripes sp{ck->key.rank, W};       // sp.count(a, b): this rank's elements of [a, b)
     size_t per = 0;
-    for (size_t j = 0; j < chunks; ++j) per = std::max(per, local(cut[j], cut[j + 1]));
+    for (size_t j = 0; j < chunks; ++j) per = std::max(per, sp.count(cut[j], cut[j + 1]));
     if (!ck->copy_stream) SRS_HIP_CHECK(hipStreamCreateWithFlags(&ck->copy_stream, hipStreamNonBlocking));
     while (ck->events.size() < chunks + 1) {
         hipEvent_t e;
@@ -1148,36 +1075,24 @@ int commit_streamed_core(StreamRes ck_, const std::vector<Seg> &segs, size_t n, 
     std::vector<bool> launched(chunks, false);
     // every chunk on the 16-bit windows: the chunks fold their buckets into one running set and only the last one is reduced
     bool fold = chunks > 1;
-    for (size_t j = 0; j < chunks; ++j) fold = fold && local(cut[j], cut[j + 1]) > 0;
+    for (size_t j = 0; j < chunks; ++j) fold = fold && sp.count(cut[j], cut[j + 1]) > 0;
     msm::reserve(ck->key, (uint32_t)per, 1);
-    auto upload = [&](size_t j) {
-        if (W == 1) {
-            upload_range(dst, segs, cut[j], cut[j + 1], ck->copy_stream);
-        } else {                             // the rank's stripes of [cut_j, cut_j+1): strided copies per piece, strided memsets for the padding
-            const size_t up = upload_stripes(dst, segs, n, cut[j], cut[j + 1], R, W, ck->copy_stream);
-            if (ck->h2d_bytes) *ck->h2d_bytes += up * sizeof(fe_t);
-        }
+    auto upload_chunk = [&](size_t j) {    // the rank's stripes of [cut_j, cut_j+1): copies per piece, memsets for the padding (world == 1: all of it)
+        const size_t up = upload(dst, segs, cut[j], cut[j + 1], sp, ck->copy_stream);
+        if (ck->h2d_bytes) *ck->h2d_bytes += up * sizeof(fe_t);
         SRS_HIP_CHECK(hipEventRecord(ck->events[j], ck->copy_stream));
-        if (ck->h2d_bytes && W == 1) *ck->h2d_bytes += (cut[j + 1] - cut[j]) * sizeof(fe_t);
         if (ck->peer_dst && W > 1) {         // the same stripes, from this device's landing buffer to the process's device copy
             SRS_HIP_CHECK(hipStreamWaitEvent(ck->peer_stream, ck->events[j], 0));
-            const size_t len = cut[j + 1] - cut[j], full = len / SL;
-            const size_t mine = full > R ? (full - R + W - 1) / W : 0;
-            const fe_t *d = dst + cut[j];
-            fe_t *pd = ck->peer_dst + cut[j];
-            if (mine)
-                SRS_HIP_CHECK(hipMemcpy2DAsync(pd + R * SL, W * SL * sizeof(fe_t), d + R * SL, W * SL * sizeof(fe_t), SL * sizeof(fe_t), mine,
-                                               hipMemcpyDefault, ck->peer_stream));      // (peer access was checked when the key was made)
-            if (len % SL && full % W == R)
-                SRS_HIP_CHECK(hipMemcpyAsync(pd + full * SL, d + full * SL, (len % SL) * sizeof(fe_t), hipMemcpyDefault, ck->peer_stream));
-            if (ck->peer_bytes) *ck->peer_bytes += local(cut[j], cut[j + 1]) * sizeof(fe_t);
+            const size_t fwd = stripe_copy(sp, cut[j], cut[j + 1], ck->peer_dst, false, dst, 0, hipMemcpyDefault,
+                                           ck->peer_stream);                             // (peer access was checked when the key was made)
+            if (ck->peer_bytes) *ck->peer_bytes += fwd * sizeof(fe_t);
         }
     };
     auto launch = [&](size_t j) {
         const fe_t *ptr = dst + cut[j];
         // sharded: nn local scalars of the chunk, read through the stripe map relative to ptr (cut_j is a multiple of world * 2^10);
         // their bases start at local index cut_j / world
-        const uint32_t nn = (uint32_t)local(cut[j], cut[j + 1]), base = (uint32_t)(W == 1 ? cut[j] : cut[j] / W);
+        const uint32_t nn = (uint32_t)sp.count(cut[j], cut[j + 1]), base = (uint32_t)(W == 1 ? cut[j] : cut[j] / W);
         if (nn == 0) {                       // a rank without a stripe in this chunk (ragged end)
             SRS_HIP_CHECK(hipStreamWaitEvent(st, ck->events[j], 0));
             return;
@@ -1192,13 +1107,13 @@ int commit_streamed_core(StreamRes ck_, const std::vector<Seg> &segs, size_t n, 
     // the copy of chunk j + 1 (r06: with the r05 order MSM j could only be queued after upload j + 1 had returned -- the device ran one
     // chunk behind the link, +1.3 ms on the k = 20 step, bench.py secondary.pageable_witness)
     const bool pageable = !segs.empty() && segs[0].len && host_is_pageable(segs[0].src);
-    upload(0);
+    upload_chunk(0);
     for (size_t j = 0; j < chunks; ++j) {
         if (pageable) {
             launch(j);
-            if (j + 1 < chunks) upload(j + 1);
+            if (j + 1 < chunks) upload_chunk(j + 1);
         } else {
-            if (j + 1 < chunks) upload(j + 1);
+            if (j + 1 < chunks) upload_chunk(j + 1);
             launch(j);
         }
     }
@@ -1215,12 +1130,12 @@ int commit_streamed_core(StreamRes ck_, const std::vector<Seg> &segs, size_t n, 
         used_slots.push_back((uint32_t)j);
         missed = missed || msm::overflow_missed(ck->key, (uint32_t)j);
     }
-    msm::note_commit(ck->key, used_slots.data(), (uint32_t)used_slots.size(), local(0, n));   // + the scalars: the density the next commit's cuts follow
+    msm::note_commit(ck->key, used_slots.data(), (uint32_t)used_slots.size(), sp.count(0, n));   // + the scalars: the density the next commit's cuts follow
     xyzz_t redo;
     if (missed) {
         ++ck->key.stat_redo;
         const fe_t *whole = dst;
-        const uint32_t n_local = (uint32_t)local(0, n);
+        const uint32_t n_local = (uint32_t)sp.count(0, n);
         msm::run(ck->key, &whole, &n_local, 1, repr == SRS_REPR_MONT, st, &redo);
         ht.mark("overflow redo");
     }
@@ -1311,7 +1226,7 @@ std::vector<size_t> commit_cuts(size_t n, size_t align, size_t n_eff = 0, double
 int multi_commit_streamed(srs_ck *ck, const std::vector<Seg> &segs, size_t n, fe_t *dev_copy, int repr, hipStream_t st, srs_affine *out) {
     const uint32_t world = (uint32_t)ck->shards.size();
     const int home = home_device();
-    const size_t align = (size_t)world << msm::STRIPE_LOG;
+    const size_t align = (size_t)world << STRIPE_LOG;
     const std::vector<size_t> cut = commit_cuts(n, align, n / world, key_density(ck->shards[0]->key));
     std::vector<xyzz_t> parts(world);
     hipEvent_t ready = nullptr;
@@ -1402,12 +1317,12 @@ int srs_commit_upload(srs_ck *ck, const srs_fe *scalars_host, size_t n, srs_fe *
         // bytes over this GPU's link, in chunks whose upload overlaps the MSM of the previous chunk (commit_streamed); the other
         // stripes of dev_copy are left as they are
         return guarded([&]() -> int {
-            const size_t align = (size_t)ck->key.world << msm::STRIPE_LOG;
+            const size_t align = (size_t)ck->key.world << STRIPE_LOG;
             std::vector<Seg> segs(1, Seg{reinterpret_cast<const fe_t *>(scalars_host), 0, n});
             return commit_streamed(ck, segs, n, commit_cuts(n, align, n / ck->key.world, key_density(ck->key)), reinterpret_cast<fe_t *>(dev_copy), repr, st, out);
         });
     }
-    if (!ck->shards.empty() && n >= ((size_t)ck->shards.size() << (msm::STRIPE_LOG + 1))) {
+    if (!ck->shards.empty() && n >= ((size_t)ck->shards.size() << (STRIPE_LOG + 1))) {
         // multi-device key: every shard streams its stripes over its own link, overlapped with its MSM; the device copy is assembled on the
         // process's device by peer copies (multi_commit_streamed)
         return guarded([&]() -> int {
@@ -1460,7 +1375,7 @@ int srs_concat_with_padding(srs_fe *out_dev, const srs_fe *const *columns_host, 
             segs.push_back(Seg{reinterpret_cast<const fe_t *>(columns_host[c]), off, lens[c]});
             off += std::max(lens[c], pad_size);
         }
-        upload_range(reinterpret_cast<fe_t *>(out_dev), segs, 0, off, (hipStream_t)stream);
+        upload(reinterpret_cast<fe_t *>(out_dev), segs, 0, off, Stripes{0, 1}, (hipStream_t)stream);
         return SRS_OK;
     });
 }
@@ -1488,10 +1403,10 @@ int srs_commit_upload_columns(srs_ck *ck, const srs_fe *const *columns_host, con
             off += std::max(lens[c], pad_size);
         }
         fe_t *dst = reinterpret_cast<fe_t *>(dev_copy);
-        if (!ck->shards.empty() && n >= ((size_t)ck->shards.size() << (msm::STRIPE_LOG + 1)))
+        if (!ck->shards.empty() && n >= ((size_t)ck->shards.size() << (STRIPE_LOG + 1)))
             // multi-device key (r05): every shard streams ITS stripes of the columns (and of their zero padding) over its own link
             return multi_commit_streamed(ck, segs, n, dst, repr, st, out);
-        const bool sharded_streamed = ck->shards.empty() && ck->key.world > 1 && n >= ((size_t)ck->key.world << (msm::STRIPE_LOG + 1));
+        const bool sharded_streamed = ck->shards.empty() && ck->key.world > 1 && n >= ((size_t)ck->key.world << (STRIPE_LOG + 1));
         const bool streamed = ck->shards.empty() && (ck->key.world == 1 || sharded_streamed) && n != 0;
         if (!dst) {
             ck->staging.reserve(Arena::pad((n + 1) * sizeof(fe_t)) + 256);
@@ -1499,11 +1414,11 @@ int srs_commit_upload_columns(srs_ck *ck, const srs_fe *const *columns_host, con
             dst = ck->staging.take<fe_t>(n + 1);
         }
         if (!streamed) {                     // (short vectors on multi-device / sharded keys) assemble in HBM, then the ordinary commit
-            upload_range(dst, segs, 0, n, st);
+            upload(dst, segs, 0, n, Stripes{0, 1}, st);
             return srs_commit(ck, reinterpret_cast<const srs_fe *>(dst), n, SRS_SPACE_DEVICE, repr, stream, out);
         }
         if (sharded_streamed)                // process-sharded key (r05): the rank's stripes of the columns, chunk boundaries on world * 2^10
-            return commit_streamed(ck, segs, n, commit_cuts(n, (size_t)ck->key.world << msm::STRIPE_LOG, n / ck->key.world, key_density(ck->key)), dst,
+            return commit_streamed(ck, segs, n, commit_cuts(n, (size_t)ck->key.world << STRIPE_LOG, n / ck->key.world, key_density(ck->key)), dst,
                                    repr, st, out);
         const size_t align = (uniform && pad_size >= 1024) ? pad_size : 1024;
         std::vector<size_t> cut = commit_cuts(n, align, 0, key_density(ck->key));
@@ -1801,20 +1716,20 @@ int srs_structure_set_shard(srs_structure *S, uint32_t rank, uint32_t world) {
 // every ProtoGalaxy leaf sits at row 0 (reference_compat, src/plonk/mod.rs:714).  Sorted, unique.
 static std::vector<size_t> shard_halo_rows(const srs_structure *S, int reference_compat) {
     const uint32_t world = rowprog::shard_world(S->s), rank = rowprog::shard_rank(S->s);
-    const size_t rows = rowprog::rows(S->s), SL = (size_t)1 << rowprog::ROW_STRIPE_LOG;
+    const Stripes sp{rank, world};
+    const size_t rows = rowprog::rows(S->s);
     int32_t lo = 0, hi = 0;
     rowprog::rotation_range(S->s, &lo, &hi);
-    auto own = [&](size_t row) { return (row >> rowprog::ROW_STRIPE_LOG) % world == rank; };
     std::vector<size_t> need;
     auto add_row = [&](int64_t r) {
         const size_t row = (size_t)(((r % (int64_t)rows) + (int64_t)rows) % (int64_t)rows);
-        if (!own(row)) need.push_back(row);
+        if (!sp.owns(row)) need.push_back(row);
     };
     if (lo < 0 || hi > 0) {
-        for (size_t s = rank; s < rows / SL; s += world) {
-            for (int64_t r = lo; r < 0; ++r) add_row((int64_t)(s * SL) + r);
-            for (int64_t r = 0; r < hi; ++r) add_row((int64_t)((s + 1) * SL) + r);
-        }
+        sp.each_piece(0, rows, [&](size_t first, size_t, size_t len) {              // every stripe of this rank (rows is a multiple of the stripe)
+            for (int64_t r = lo; r < 0; ++r) add_row((int64_t)first + r);
+            for (int64_t r = 0; r < hi; ++r) add_row((int64_t)(first + len) + r);
+        });
     }
     if (reference_compat)
         for (int64_t r = lo; r <= hi; ++r) add_row(r);
@@ -1828,9 +1743,9 @@ int srs_structure_fold_sharded(srs_structure *S, srs_fe *out, const srs_fe *cons
                                void *stream) {
     if (!S || !out || !W || !coefs || J == 0) return fail(SRS_ERR_INVALID, "srs_structure_fold_sharded: bad argument");
     const uint32_t world = rowprog::shard_world(S->s), rank = rowprog::shard_rank(S->s), k = rowprog::log_rows(S->s);
-    const size_t rows = rowprog::rows(S->s), cols = rowprog::num_witness_columns(S->s), SL = (size_t)1 << rowprog::ROW_STRIPE_LOG;
+    const size_t rows = rowprog::rows(S->s), cols = rowprog::num_witness_columns(S->s), SL = (size_t)1 << STRIPE_LOG;
     const int field = rowprog::field(S->s);
-    if (world > 1 && (k < rowprog::ROW_STRIPE_LOG || (rows / SL) % world != 0))
+    if (world > 1 && (k < STRIPE_LOG || (rows / SL) % world != 0))
         return fail(SRS_ERR_INVALID, "srs_structure_fold_sharded: 2^k / 2^10 is not a multiple of the world size -- the row stripes of the "
                                      "columns do not coincide with the key's stripes; fold the whole vector (srs_fold_lincomb)");
     int rc = ensure_device();
@@ -1874,8 +1789,8 @@ int srs_structure_upload_shard_halo(const srs_structure *S, const srs_fe *witnes
     const size_t rows = rowprog::rows(S->s), cols = rowprog::num_witness_columns(S->s);
     if (n != rows * cols) return fail(SRS_ERR_INVALID, "srs_structure_upload_shard_halo: n is not num_witness_columns * 2^k");
     if (world <= 1) return SRS_OK;
-    const size_t SL = (size_t)1 << rowprog::ROW_STRIPE_LOG;
-    if (k < rowprog::ROW_STRIPE_LOG || (rows / SL) % world != 0)
+    const size_t SL = (size_t)1 << STRIPE_LOG;
+    if (k < STRIPE_LOG || (rows / SL) % world != 0)
         return fail(SRS_ERR_INVALID, "srs_structure_upload_shard_halo: 2^k / 2^10 is not a multiple of the world size -- the row stripes of the "
                                      "columns do not coincide with the key's stripes; upload the whole witness instead");
     int rc = ensure_device();

@@ -3,6 +3,7 @@
 #include "curve.cuh"
 #include "devrt.h"
 #include "glv.cuh"
+#include "stripes.h"     // STRIPE_LOG, Stripes: the multi-GPU block-cyclic sharding
 #include "tuning.h"
 
 #include <cstdlib>
@@ -15,7 +16,6 @@ constexpr int NWIN = 16;                  // ceil(256 / WBITS); scalars are < 2^
 constexpr int NWIN_COMPACT = 8;           // windows a compact key stores: digit rows 8..15 are the windows 0..7 of phi(P) (glv.cuh)
 constexpr uint32_t PAY_ENDO = 1u << 30;   // compact keys: the entry's point is phi of the table entry (bit 31 is the sign, the index lies below)
 constexpr uint32_t NBUCKET = 1u << (WBITS - 1);   // |digit| in 1..2^15 -> bucket |digit|-1
-constexpr uint32_t STRIPE_LOG = 10;       // multi-GPU block-cyclic stripe (entries)
 
 constexpr uint32_t SORT_THREADS = 1024;   // one workgroup per CU: 128 KiB LDS histogram
 constexpr uint32_t SORT_TILE_MIN = 8192;       // digits per workgroup (lower bound)

@@ -69,14 +69,6 @@ __device__ __forceinline__ uint32_t upper_bucket(const uint32_t *__restrict__ tp
     return lo;
 }
 
-// global index of local scalar i under block-cyclic sharding (stripe = 2^STRIPE_LOG entries):
-// rank r of `world` owns stripes s with s % world == r.
-__device__ __forceinline__ size_t shard_global_index(size_t i, uint32_t rank, uint32_t world) {
-    if (world == 1) return i;
-    size_t s = i >> STRIPE_LOG, o = i & ((1u << STRIPE_LOG) - 1);
-    return ((s * world + rank) << STRIPE_LOG) + o;
-}
-
 // ---------------------------------------------------------------------------------------------
 // key expansion: T[w][i] = 2^(16 w) P_i
 // ---------------------------------------------------------------------------------------------
@@ -166,7 +158,7 @@ __global__ void k_gen_bases(xyzz_t *__restrict__ tmp, uint32_t n, uint64_t seed,
     using F = typename C::F;
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    uint64_t g = shard_global_index(i, rank, world);
+    uint64_t g = Stripes{rank, world}.global_index((size_t)i);
     uint64_t st = seed ^ (g * 0x100000001b3ull + 0xcbf29ce484222325ull);
     uint32_t k[8];
     for (int j = 0; j < 4; ++j) {
@@ -239,7 +231,7 @@ __global__ void k_digits(BatchDesc bd, uint16_t *__restrict__ dig, size_t dig_st
     for (uint32_t j = (blockIdx.y * gridDim.x + blockIdx.x) * blockDim.x + threadIdx.x; j < n_zero; j += gridDim.x * gridDim.y * blockDim.x)
         count_zero[j] = 0;
     if (i >= n) return;
-    fe_t s = bd.ptr[m][shard_global_index(i, rank, world)];
+    fe_t s = bd.ptr[m][Stripes{rank, world}.global_index((size_t)i)];
     if (is_mont) s = S::from_mont(s);
     uint16_t *d = dig + (size_t)m * dig_stride;
     if (COMPACT) {                            // k = k1 + lambda k2: rows 0..7 from |k1|, rows 8..15 from |k2| (entries of phi(P), see k_scatter)
@@ -609,7 +601,7 @@ __device__ __forceinline__ void wide_codes(const WideDesc &wd, uint32_t i, uint3
         for (int w = 0; w < NWIN_W; ++w) code[w] = 0xFFFFFFFFu;
         return;
     }
-    fe_t s = wd.ptr[shard_global_index(i, wd.rank, wd.world)];
+    fe_t s = wd.ptr[Stripes{wd.rank, wd.world}.global_index((size_t)i)];
     if (wd.is_mont) s = S::from_mont(s);
     uint32_t carry = 0;
 #pragma unroll

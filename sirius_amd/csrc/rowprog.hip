@@ -138,7 +138,7 @@ struct PgArgs {
     uint32_t wpts;            // P (F) or 1 (G, e)
     uint32_t tile_log;        // leaves per workgroup = 2^tile_log (<= 7)
     fe_t *partial;            // [n_gates * tiles_per_gate][P]
-    uint32_t shard_rank, shard_world;   // process-per-GPU runs (set_shard): a 1024-leaf tile IS a key stripe (ROW_STRIPE_LOG), this rank
+    uint32_t shard_rank, shard_world;   // process-per-GPU runs (set_shard): a 1024-leaf tile IS a key stripe (STRIPE_LOG), this rank
                               //   evaluates the tiles t % world == rank and leaves zeros for the others: its result is a PARTIAL sum
     // reference leaf rows (compat): every leaf of a gate is that gate AT ROW 0 -- one value per (gate, point) for the whole launch.  r03 shared it
     // among the 8 leaves of a thread; r04 hoists it out of the leaf pass: a one-workgroup launch (hoist_mode 1) evaluates the gates and leaves
@@ -741,7 +741,7 @@ __global__ void k_lincomb(fe_t *__restrict__ out, LincombArgs a, size_t n, uint3
     size_t l = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     size_t stride = (size_t)gridDim.x * blockDim.x;
     for (; l < n; l += stride) {
-        const size_t i = world <= 1 ? l : ((((l >> ROW_STRIPE_LOG) * world + rank) << ROW_STRIPE_LOG) + (l & ((1u << ROW_STRIPE_LOG) - 1)));
+        const size_t i = Stripes{rank, world}.global_index(l);
         fe_t acc;
         if (AFFINE) {
             const fe_t w0 = a.w[0][i];
@@ -960,14 +960,6 @@ void destroy(Structure *S) {
     delete S;
 }
 
-static uint32_t shard_local_rows(size_t rows, uint32_t rank, uint32_t world) {     // rows of this rank's block-cyclic stripes
-    if (world <= 1) return (uint32_t)rows;
-    const size_t Sz = (size_t)1 << ROW_STRIPE_LOG, full = rows >> ROW_STRIPE_LOG, rem = rows & (Sz - 1);
-    size_t cnt = (full / world) * Sz;
-    if (rank < full % world) cnt += Sz;
-    if (rank == full % world) cnt += rem;
-    return (uint32_t)cnt;
-}
 void set_shard(Structure *S, uint32_t rank, uint32_t world) {
     S->shard_rank = rank;
     S->shard_world = world ? world : 1;
@@ -1069,7 +1061,7 @@ static int evaluate_prog(Structure *S, Program &p, int mode, const fe_t *W1_dev,
     // only); the deciders' plain evaluations always cover every row
     a.ctx.shard_rank = mode == 0 ? S->shard_rank : 0;
     a.ctx.shard_world = mode == 0 ? S->shard_world : 1;
-    a.ctx.local_rows = shard_local_rows(S->rows, a.ctx.shard_rank, a.ctx.shard_world);
+    a.ctx.local_rows = (uint32_t)Stripes{a.ctx.shard_rank, a.ctx.shard_world}.count(S->rows);
     a.utab = d_utab;
     a.n_uniform = (uint32_t)nu;
     a.npts = npts;
@@ -1351,7 +1343,7 @@ int pg_sum(Structure *S, int mode, const fe_t *const *W_dev, const fe_t *const *
         a.wpts = 1;
         a.tile_log = tile_log;
         a.partial = nullptr;
-        a.shard_rank = S->shard_rank;                      // lpt == 8 here: tile_log == ROW_STRIPE_LOG
+        a.shard_rank = S->shard_rank;                      // lpt == 8 here: tile_log == STRIPE_LOG
         a.shard_world = S->shard_world;
         a.hoist = d_hoist;
         a.hoist_mode = 0;
@@ -1475,7 +1467,7 @@ int pg_sum(Structure *S, int mode, const fe_t *const *W_dev, const fe_t *const *
     a.tile_log = tile_log;
     a.partial = buf0;
     // partial sums of a sharded structure: by tiles when a tile is a stripe (k >= 10), else rank 0 evaluates everything
-    if (tile_log == ROW_STRIPE_LOG) { a.shard_rank = S->shard_rank; a.shard_world = S->shard_world; }
+    if (tile_log == STRIPE_LOG) { a.shard_rank = S->shard_rank; a.shard_world = S->shard_world; }
     else if (S->shard_world > 1 && S->shard_rank != 0) { a.shard_rank = 0xFFFFFFFFu; a.shard_world = 2; }     // no tile is mine
     else { a.shard_rank = 0; a.shard_world = 1; }
     {
@@ -1843,15 +1835,8 @@ size_t log_derivative_mismatches(Structure *S, const fe_t *W_dev, hipStream_t st
 int lincomb(int field, fe_t *out, const fe_t *const *w_dev, const fe_t *coefs, size_t J, size_t n, hipStream_t st, std::string &err,
             uint32_t rank, uint32_t world) {
     if (J == 0 || J > JMAX) { err = "unsupported number of witnesses"; return 4; }
-    if (world > 1) {                           // elements of this rank's stripes (block-cyclic, 2^ROW_STRIPE_LOG each)
-        const size_t SL = (size_t)1 << ROW_STRIPE_LOG, full = n / SL;
-        size_t mine = (full > rank ? (full - rank + world - 1) / world : 0) * SL;
-        if (n % SL && full % world == rank) mine += n % SL;
-        n = mine;
-    } else {
-        rank = 0;
-        world = 1;
-    }
+    if (world <= 1) { rank = 0; world = 1; }
+    n = Stripes{rank, world}.count(n);         // the elements of this rank's stripes
     if (!n) return 0;
     LincombArgs a;
     a.J = (uint32_t)J;

@@ -4,6 +4,7 @@
 #include "field.cuh"
 #include "field29.cuh"
 #include "lanes.cuh"      // SRS_SWEEP_ACC
+#include "stripes.h"      // STRIPE_LOG, Stripes: rows are sharded like the key's entries
 
 namespace srs {
 namespace rowprog {
@@ -30,7 +31,7 @@ struct RowCtx {
     const fe_t *wcoef;        // [npts][J] combination coefficients, or nullptr:
                               //   J == 1: W[0];  J == 2: W[0] + pt * W[1]  (cross-term points X = pt)
     uint32_t shard_rank, shard_world, local_rows;   // multi-GPU: this rank evaluates only the rows of ITS block-cyclic stripes
-                              //   (2^ROW_STRIPE_LOG rows each, the stripes of the sharded commitment key); world == 1: all rows
+                              //   (2^STRIPE_LOG rows each, the stripes of the sharded commitment key); world == 1: all rows
     uint32_t half;            // J == 2, wcoef == nullptr: (W[0] + W[1]) / 2 + pt * (W[0] - W[1]) / 2, i.e. the Lagrange fold
                               //   L_0(X) W[0] + L_1(X) W[1] over the domain {1, -1} at the integer point X = pt (compute_G, L = 1)
     uint32_t pt0;             // sweep form only: the first evaluation point is X = pt0 instead of X = 0 (compute_G skips X = 1 when the
@@ -121,8 +122,6 @@ __device__ __forceinline__ void adv_affine(const RowCtx &C, uint32_t col, uint32
     for (uint32_t i = 0; i < C.pt0; ++i) cur = F::add(cur, step);
 }
 
-constexpr uint32_t ROW_STRIPE_LOG = 10;   // == msm::STRIPE_LOG: rows and key entries are sharded alike
-
 // thread index -> (row to evaluate, whether it exists).  Under sharding thread t is the t-th row of this rank's stripes.
 __device__ __forceinline__ uint32_t shard_row(const RowCtx &C, uint32_t t, bool &live) {
     if (C.shard_world <= 1) {
@@ -131,8 +130,7 @@ __device__ __forceinline__ uint32_t shard_row(const RowCtx &C, uint32_t t, bool 
     }
     live = t < C.local_rows;
     if (!live) t = C.local_rows ? C.local_rows - 1 : 0;
-    const uint32_t s = t >> ROW_STRIPE_LOG, o = t & ((1u << ROW_STRIPE_LOG) - 1);
-    const uint32_t row = ((s * C.shard_world + C.shard_rank) << ROW_STRIPE_LOG) + o;
+    const uint32_t row = Stripes{C.shard_rank, C.shard_world}.global_index(t);
     if (row >= C.rows) { live = false; return C.rows - 1; }
     return row;
 }

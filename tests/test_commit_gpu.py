@@ -629,7 +629,7 @@ def _concat_cases(S, O, cid, make_dev, k=11):
     mk.close()
     ck.close()
     # r05: the column form STREAMS on sharded keys too -- every shard / rank uploads its own stripes of the columns and memsets its stripes of the
-    # padding (upload_stripes): (a) a multi-device key with a device copy assembled by peer copies, bytes per link = the data elements of the
+    # padding (upload with the shard's Stripes): (a) a multi-device key with a device copy assembled by peer copies, bytes per link = the data elements of the
     # shard's stripes; (b) a key sharded over "processes": rank r's call returns its partial commitment and fills ITS stripes of its buffer
     n, SL = W.shape[0], 1024
     data = np.zeros(n, dtype=bool)
@@ -664,6 +664,14 @@ def _concat_cases(S, O, cid, make_dev, k=11):
 def test_concatenate_with_padding_and_column_commit(srs, oracle, cid):
     import torch
     _concat_cases(srs, oracle, cid, lambda n: torch.full((n, 4), 7, dtype=torch.int64, device="cuda"))
+
+
+def test_column_commit_chunk_boundary_inside_a_column(srs, oracle):
+    """tests/stripe_cases.py: a three-shard multi-device key and ranks 0..2 of world 3, four chunks, the first boundary inside the short
+    column's data -- commitment, device copy (foreign stripes untouched), bytes per link."""
+    import torch
+    from stripe_cases import run_chunk_boundary_case
+    run_chunk_boundary_case(srs, oracle, lambda n: torch.full((n, 4), 7, dtype=torch.int64, device="cuda"))
 
 
 def test_commit_vs_eip196_known_answers(srs, oracle):

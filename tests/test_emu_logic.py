@@ -286,6 +286,14 @@ def _commit_upload_and_multi_device_key(emu, O):
     mk.close()
 
 
+def test_emu_column_commit_chunk_boundary_inside_a_column(emu, oracle):
+    """tests/stripe_cases.py on the emulator: the host logic of the streamed column commit on a three-shard multi-device key and on ranks
+    0..2 of world 3, four chunks, the first boundary inside the short column's data; the GPU version is tests/test_commit_gpu.py."""
+    import torch
+    from stripe_cases import run_chunk_boundary_case
+    run_chunk_boundary_case(emu, oracle, lambda n: torch.full((n, 4), 7, dtype=torch.int64))
+
+
 def test_emu_bench_harness():
     """bench.py end to end on the emulator (tiny sizes): the harness logic -- CycleFold step order, host witness buffers,
     commit_upload with a device copy, the CPU-baseline leg (--full) -- produces the JSON line with the contract's fields."""
