@@ -72,7 +72,7 @@ const char *srs_version(void);
  * oracle can check; a deployer may set "msm_wide" = 0 to save 13/16 of a large key's HBM (also: environment SRS_MSM_WIDE=0), or
  * "msm_compact" = 1 before creating a key to halve its 16-bit-window table (8 windows + the curve endomorphism, srs_ck_is_compact).
  * Names (srs_tuning_name(i), i = 0, 1, ... until NULL): msm_sort, msm_l0, msm_wide, msm_wide_min, msm_slots, msm_slot_log,
- * msm_expect_ovf, msm_quad_max, commit_chunks, pg_f_eval, pg_g_fft, jit_always, no_jit, msm_compact.  Process-wide; set before the calls they
+ * msm_expect_ovf, msm_quad_max, commit_chunks, pg_f_eval, pg_g_fft, jit_always, no_jit, msm_compact, pg_compat_tree.  Process-wide; set before the calls they
  * affect (a value is read when a call starts).  rc SRS_ERR_INVALID for an unknown name.  No reference counterpart. */
 int srs_tuning_set(const char *name, int64_t value);
 int srs_tuning_get(const char *name, int64_t *value);        /* *value = INT64_MIN while unset */
@@ -309,7 +309,8 @@ void srs_structure_free(srs_structure *S);
  * The ProtoGalaxy sums of a sharded structure (srs_pg_compute_F / _G / srs_pg_evaluate_e) cover the leaves of the rank's tiles
  * only (a 1024-leaf tile of the leaf kernels is a stripe; structures of fewer than 2^10 rows: rank 0 evaluates everything):
  * every rank gets a PARTIAL polynomial / value, the results of all ranks add up (coefficient-wise, e.g. srs_fold_lincomb on
- * host vectors) to the polynomial of the reference.  The whole-prove entries (srs_pg_prove, srs_sangria_prove) refuse sharded
+ * host vectors) to the polynomial of the reference.  With the reference's leaf rows (reference_compat, which reads row 0 only)
+ * there is nothing to shard: rank 0 returns the whole polynomial / value and every other rank zeros -- the same total.  The whole-prove entries (srs_pg_prove, srs_sangria_prove) refuse sharded
  * handles: the challenges depend on the exchanged sums.
  * WHICH WITNESS ROWS A RANK READS.  With the WHOLE witness resident the sharded calls are correct for any circuit.  After a
  * sharded srs_commit_upload only the rank's key stripes are resident; that suffices only if ALL of these hold:
@@ -526,6 +527,12 @@ int srs_pg_compute_K_from_G(const srs_fe *poly_G, size_t n_G, const srs_fe *poly
 /* evaluate_e_from_trace (src/nifs/protogalaxy/mod.rs:571-640): e = sum_i pow_i(betas) f_i(w) */
 int srs_pg_evaluate_e(srs_structure *S, const srs_fe *betas, size_t n_betas, const srs_fe *W, const srs_fe *challenges,
                       size_t n_challenges, int space, int reference_compat, void *stream, srs_fe *e);
+/* The closed form the library evaluates these sums by under reference_compat (every leaf of a gate is that gate at row 0, see
+ * INTEGRATION.md 6b pg_compat_tree): sum_i pow_i(w) f_i over the leaves f_i = gate_values[i >> k], i < n_gates * 2^k, of a table of
+ * 2^n_weights leaves.  delta == NULL: w = weights, one value (evaluate_e, G at a point).  Else w_b = weights[b] + X delta^(2^b):
+ * n_weights + 1 coefficients (compute_F).  Needs n_gates <= 2^(n_weights - k).  Host; no reference counterpart. */
+int srs_pg_closed_form(const srs_fe *gate_values, size_t n_gates, uint32_t k, const srs_fe *weights, size_t n_weights,
+                       const srs_fe *delta, srs_fe *out);
 /* calculate_e (protogalaxy/mod.rs:748-764): F(alpha) * L_0(gamma) + Z(gamma) * K(gamma); host */
 int srs_pg_calculate_e(const srs_fe *poly_F, size_t n_F, const srs_fe *poly_K, size_t n_K, const srs_fe *gamma,
                        const srs_fe *alpha, uint32_t log_n, srs_fe *out);

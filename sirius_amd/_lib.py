@@ -126,6 +126,7 @@ def _prototypes():
         "srs_pg_compute_G": (i32, [vp, vp, sz, C.POINTER(vp), C.POINTER(vp), sz, sz, i32, i32, vp, vp]),
         "srs_pg_compute_K_from_G": (i32, [vp, sz, vp, sz, u32, vp, vp]),
         "srs_pg_evaluate_e": (i32, [vp, vp, sz, vp, vp, sz, i32, i32, vp, vp]),
+        "srs_pg_closed_form": (i32, [vp, sz, u32, vp, sz, vp, vp]),
         "srs_pg_calculate_e": (i32, [vp, sz, vp, sz, vp, vp, u32, vp]),
         "srs_lagrange_eval": (i32, [vp, u32, vp]),
         "srs_poly_eval": (i32, [vp, sz, vp, vp]),

@@ -2432,6 +2432,16 @@ int srs_poly_eval(const srs_fe *coeffs, size_t n, const srs_fe *x, srs_fe *out) 
     std::memcpy(out, &r, 32);
     return SRS_OK;
 }
+int srs_pg_closed_form(const srs_fe *gate_values, size_t n_gates, uint32_t k, const srs_fe *weights, size_t n_weights, const srs_fe *delta,
+                       srs_fe *out) {
+    if (!gate_values || !n_gates || !weights || !out || k > n_weights || n_weights > 63 || ((n_gates - 1) >> (n_weights - k)) != 0)
+        return fail(SRS_ERR_INVALID, "srs_pg_closed_form: bad argument");
+    const fe_t *c = reinterpret_cast<const fe_t *>(gate_values), *w = reinterpret_cast<const fe_t *>(weights);
+    fe_t *o = reinterpret_cast<fe_t *>(out);
+    if (delta) rowprog::pg_closed_F(c, (uint32_t)n_gates, k, w, *reinterpret_cast<const fe_t *>(delta), (uint32_t)n_weights, o, n_weights + 1);
+    else o[0] = rowprog::pg_closed_sum(c, 1, (uint32_t)n_gates, k, w, (uint32_t)n_weights);
+    return SRS_OK;
+}
 int srs_pg_calculate_e(const srs_fe *poly_F, size_t n_F, const srs_fe *poly_K, size_t n_K, const srs_fe *gamma,
                        const srs_fe *alpha, uint32_t log_n, srs_fe *out) {
     if (!poly_F || !poly_K || !gamma || !alpha || !out) return fail(SRS_ERR_INVALID, "srs_pg_calculate_e: bad argument");
@@ -2482,10 +2492,27 @@ int srs_pg_prove(srs_structure *S, srs_poseidon *ro, const srs_fe *betas, size_t
         }
         std::string err;
         size_t n_out = 0;
-        // poly_F = compute_F(betas, delta, accumulator)                                                   :417-422
-        int erc = rowprog::pg_sum(s, 0, dW.data(), ch.data(), n_challenges, 1, reinterpret_cast<const fe_t *>(betas), n_betas,
+        // the reference's leaf rows (reference_compat): every sum below is a closed form over the gates at row 0 (rowprog.hip).
+        // One launch evaluates them on the fold at each of G's points BEFORE alpha is known -- they do not depend on it -- and the point
+        // X = 1, where the fold is the accumulator, gives F's; after this D2H, F, alpha, beta' and G are host arithmetic
+        const bool closed = rowprog::pg_closed_route(reference_compat);
+        const uint32_t n_gates = (uint32_t)rowprog::num_gates(s), levels = (uint32_t)z.betas_count, log_rows = rowprog::log_rows(s);
+        rowprog::PgRow0 r0;
+        int erc = 0;
+        if (closed) {
+            erc = rowprog::pg_row0_values(s, true, dW.data(), ch.data(), n_challenges, n_instances, st, r0, err);
+            if (erc) return fail(erc, "srs_pg_prove (gates at row 0): " + err);
+            ht.mark("row0");
+            std::vector<fe_t> c0(n_gates);
+            for (uint32_t g = 0; g < n_gates; ++g) c0[g] = r0.vals[(size_t)g * r0.P + r0.one_at];
+            rowprog::pg_closed_F(c0.data(), n_gates, log_rows, reinterpret_cast<const fe_t *>(betas), *reinterpret_cast<const fe_t *>(delta), levels,
+                                 reinterpret_cast<fe_t *>(poly_F), z.points_F);
+        } else {
+            // poly_F = compute_F(betas, delta, accumulator)                                               :417-422
+            erc = rowprog::pg_sum(s, 0, dW.data(), ch.data(), n_challenges, 1, reinterpret_cast<const fe_t *>(betas), n_betas,
                                   reinterpret_cast<const fe_t *>(delta), reference_compat, st, reinterpret_cast<fe_t *>(poly_F), &n_out, err);
-        if (erc) return fail(erc, "srs_pg_prove (compute_F): " + err);
+            if (erc) return fail(erc, "srs_pg_prove (compute_F): " + err);
+        }
         ht.mark("compute_F");
         // alpha = ro.absorb(poly_F).squeeze(MAX_BITS)                                                     :424-427
         fe_t alpha, gamma;
@@ -2516,12 +2543,21 @@ int srs_pg_prove(srs_structure *S, srs_poseidon *ro, const srs_fe *betas, size_t
         // the coset ifft and the copy of K follow in the same chain of launches -- one synchronisation instead of two, no host Horner
         rowprog::PgGValues gv;
         const bool k_on_device = n_instances == 2 && z.log_domain_K <= 12;
-        erc = rowprog::pg_sum(s, 1, dW.data(), ch.data(), n_challenges, n_instances, bs.data(), bs.size(), nullptr, reference_compat, st,
-                              poly_G.data(), &n_out, err, &f_alpha, k_on_device ? &gv : nullptr);
+        std::vector<fe_t> g_vals;                              // closed form: G at its points (host)
+        if (closed)
+            rowprog::pg_closed_G(s, r0, bs.data(), levels, poly_G.data(), poly_G.size(), &g_vals);
+        else
+            erc = rowprog::pg_sum(s, 1, dW.data(), ch.data(), n_challenges, n_instances, bs.data(), bs.size(), nullptr, reference_compat, st,
+                                  poly_G.data(), &n_out, err, &f_alpha, k_on_device ? &gv : nullptr);
         if (erc) return fail(erc, "srs_pg_prove (compute_G): " + err);
         if (gv.vals_dev && !rowprog::pg_K_device_ok(gv, z.log_domain_K)) return fail(SRS_ERR_DEVICE, "srs_pg_prove: internal (device K on an unsupported shape)");
         ht.mark("compute_G");
-        if (gv.vals_dev)
+        // closed form, one incoming trace, small K domain: K's points from G's node values on the device as well (a 160-byte H2D in front);
+        // measured against the host's 256 Horner evaluations in profiles/pg_closed_form_ab.txt
+        if (closed && k_on_device && r0.g_int && g_vals.size() <= 32)
+            erc = rowprog::pg_K_from_G_values(s, g_vals.data(), (uint32_t)g_vals.size(), f_alpha, z.instances_to_fold, z.log_domain_K, st,
+                                              reinterpret_cast<fe_t *>(poly_K), err);
+        else if (gv.vals_dev)
             erc = rowprog::pg_K_from_G_device(s, gv, f_alpha, z.instances_to_fold, z.log_domain_K, st, reinterpret_cast<fe_t *>(poly_K), err);
         else
             erc = rowprog::pg_K_from_G(poly_G.data(), poly_G.size(), f_alpha, z.instances_to_fold, z.log_domain_K, st,

@@ -49,6 +49,21 @@ struct PgSizes {   // PolyContext, src/nifs/protogalaxy/poly/mod.rs:205-269
 bool pg_sizes(const Structure *S, size_t traces_len, PgSizes &out);
 std::vector<fe_t> lagrange_eval(const fe_t &X, uint32_t log_n);
 fe_t poly_eval(const fe_t *coeffs, size_t n, const fe_t &x);
+// The reference's leaf rows in closed form (reference_compat unless tuning pg_compat_tree; rowprog.hip): the gates at row 0,
+// vals[gate * P + p], on one trace (P = 1) or on the fold at compute_G's P evaluation points, and the host sums over them
+struct PgRow0 {
+    std::vector<fe_t> vals;
+    uint32_t P = 0, one_at = 0;          // one_at: the index of the point X = 1, where the fold is the accumulator W_dev[0]
+    bool g_int = false;                  // the points are the integers 0 .. P - 1 (one incoming trace), else the P roots of unity
+};
+bool pg_closed_route(int compat);
+int pg_row0_values(Structure *S, bool fold, const fe_t *const *W_dev, const fe_t *const *challenges_host, size_t n_ch, size_t J, hipStream_t st,
+                   PgRow0 &out, std::string &err);
+fe_t pg_closed_sum(const fe_t *c, size_t stride, uint32_t n_gates, uint32_t k, const fe_t *w, uint32_t levels);
+void pg_closed_F(const fe_t *c, uint32_t n_gates, uint32_t k, const fe_t *betas, const fe_t &delta, uint32_t levels, fe_t *out, size_t n_out);
+void pg_closed_G(const Structure *S, const PgRow0 &r0, const fe_t *betas_stroke, uint32_t levels, fe_t *out, size_t n_out,
+                 std::vector<fe_t> *point_values = nullptr);
+size_t num_gates(const Structure *S);
 // compute_G's values left ON THE DEVICE for pg_K_from_G_device (r06): G at the integer nodes node0 .. node0 + n_vals - 1 (the first one
 // is `g_at_one`, a host value, when skip_one), valid until the structure's next pg_* call
 struct PgGValues {
@@ -64,6 +79,8 @@ int pg_sum(Structure *S, int mode, const fe_t *const *W_dev, const fe_t *const *
 bool pg_K_device_ok(const PgGValues &g, uint32_t log_domain_K);
 int pg_K_from_G_device(Structure *S, const PgGValues &g, const fe_t &f_alpha, size_t instances_to_fold, uint32_t log_domain_K, hipStream_t st,
                        fe_t *out_host, std::string &err);
+int pg_K_from_G_values(Structure *S, const fe_t *vals_host, uint32_t n, const fe_t &f_alpha, size_t instances_to_fold, uint32_t log_domain_K,
+                       hipStream_t st, fe_t *out_host, std::string &err);
 int pg_K_from_G(const fe_t *polyG_host, size_t nG, const fe_t &f_alpha, size_t instances_to_fold, uint32_t log_domain_K,
                 hipStream_t st, fe_t *out_host, std::string &err);
 // world > 1: only the elements of rank's block-cyclic stripes (2^10 each) of out[0 .. n) are written

@@ -974,6 +974,7 @@ size_t num_advice(const Structure *S) { return S->num_advice; }
 size_t num_witness_columns(const Structure *S) { return S->num_advice + 5 * S->num_lookups; }
 size_t num_lookups(const Structure *S) { return S->num_lookups; }
 size_t rows(const Structure *S) { return S->rows; }
+size_t num_gates(const Structure *S) { return S->gate_progs.size(); }
 int field(const Structure *S) { return S->field; }
 
 template <class F>
@@ -1188,6 +1189,203 @@ static void launch_pg_leaves(const PgArgs &A, uint32_t tiles, uint32_t gates, ui
     else SRS_LAUNCH((k_pg_leaves<Fr, NS, 1>), (tiles, gates), (threads), 0, st, A);
 }
 
+// ---------------------------------------------------------------------------------------------
+// The reference's leaf rows in closed form (reference_compat).  Every leaf of gate g is that gate AT ROW 0
+// (src/plonk/mod.rs:714), one value c_g per (gate, point), and the weights are products over the index bits, pow_i(w) =
+// prod_b w_b^bit_b(i), so the sum over gate g's aligned block of 2^k leaves factors:
+//   sum_i pow_i(w) f_i = [prod_{b < k} (1 + w_b)] * sum_g c_g prod_{b >= k, bit_(b-k)(g) = 1} w_b        (padded blocks: no term)
+// The device evaluates the gates at row 0 (pg_row0_values: one launch, one D2H of n_gates x points values); the sums are host
+// arithmetic -- exact, hence the coefficients of the weighted trees bit for bit (those stay reachable: tuning pg_compat_tree).
+// ---------------------------------------------------------------------------------------------
+// evaluate_e and G at one point: c[g * stride], weights w[0 .. levels)
+fe_t pg_closed_sum(const fe_t *c, size_t stride, uint32_t n_gates, uint32_t k, const fe_t *w, uint32_t levels) {
+    fe_t acc = Fr::zero();
+    for (uint32_t g = 0; g < n_gates; ++g) {
+        fe_t t = c[(size_t)g * stride];
+        for (uint32_t b = k; b < levels; ++b)
+            if ((g >> (b - k)) & 1u) t = Fr::mul(t, w[b]);
+        acc = Fr::add(acc, t);
+    }
+    for (uint32_t b = 0; b < k && b < levels; ++b) acc = Fr::mul(acc, Fr::add(Fr::one(), w[b]));
+    return acc;
+}
+
+// compute_F: the same sum with the weights beta_b + X delta^(2^b), a product of linear polynomials: out[0 .. n_out), degree <= levels
+void pg_closed_F(const fe_t *c, uint32_t n_gates, uint32_t k, const fe_t *betas, const fe_t &delta, uint32_t levels, fe_t *out, size_t n_out) {
+    std::vector<fe_t> deltas(levels);
+    {
+        fe_t d = delta;                                        // deltas: delta^(2^b)  (:97-99)
+        for (uint32_t b = 0; b < levels; ++b) { deltas[b] = d; d = Fr::sqr(d); }
+    }
+    // p(X) *= (a + X d), deg = current degree
+    auto mul_linear = [](std::vector<fe_t> &p, uint32_t &deg, const fe_t &a, const fe_t &d) {
+        p[deg + 1] = Fr::mul(p[deg], d);
+        for (uint32_t m = deg; m >= 1; --m) p[m] = Fr::add(Fr::mul(p[m], a), Fr::mul(p[m - 1], d));
+        p[0] = Fr::mul(p[0], a);
+        ++deg;
+    };
+    std::vector<fe_t> sum(levels + 2, Fr::zero()), t(levels + 2);
+    for (uint32_t g = 0; g < n_gates; ++g) {
+        std::fill(t.begin(), t.end(), Fr::zero());
+        t[0] = c[g];
+        uint32_t deg = 0;
+        for (uint32_t b = k; b < levels; ++b)
+            if ((g >> (b - k)) & 1u) mul_linear(t, deg, betas[b], deltas[b]);
+        for (uint32_t m = 0; m <= deg; ++m) sum[m] = Fr::add(sum[m], t[m]);
+    }
+    uint32_t deg = levels > k ? levels - k : 0;
+    for (uint32_t b = 0; b < k && b < levels; ++b) mul_linear(sum, deg, Fr::add(Fr::one(), betas[b]), deltas[b]);
+    for (size_t m = 0; m < n_out; ++m) out[m] = m <= deg ? sum[m] : Fr::zero();
+}
+
+// compute_G from its gate values (PgRow0 of the folds): the point values by pg_closed_sum, then the interpolation of the route
+// the values were taken on -- the constant inverse Vandermonde matrix of the integer nodes 0 .. d_G, or the inverse DFT over the
+// P roots of unity (fft::ifft, :419; P <= 64 values: the plain sum on the host, no launch)
+void pg_closed_G(const Structure *S, const PgRow0 &r0, const fe_t *betas_stroke, uint32_t levels, fe_t *out, size_t n_out, std::vector<fe_t> *point_values) {
+    const uint32_t n_gates = (uint32_t)S->gate_progs.size(), P = r0.P;
+    std::vector<fe_t> val(P);
+    for (uint32_t p = 0; p < P; ++p) val[p] = pg_closed_sum(r0.vals.data() + p, P, n_gates, S->k, betas_stroke, levels);
+    if (point_values) *point_values = val;
+    for (size_t m = 0; m < n_out; ++m) out[m] = Fr::zero();
+    if (r0.g_int) {
+        const uint32_t dG = P - 1;
+        FieldOps f{0};
+        const std::vector<fe_t> vinv = !S->vinv_g.empty() ? S->vinv_g : (dG ? inverse_vandermonde_rows(f, dG) : std::vector<fe_t>());    // [dG][dG + 1], rows k = 1..dG
+        out[0] = val[0];                                                                            // G(0)
+        for (uint32_t k = 1; k <= dG && k < n_out; ++k) {
+            fe_t acc = Fr::zero();
+            for (uint32_t j = 0; j < P; ++j) acc = Fr::add(acc, Fr::mul(vinv[(size_t)(k - 1) * P + j], val[j]));
+            out[k] = acc;
+        }
+        return;
+    }
+    const fe_t winv = ntt::omega(ilog2(P), true), inv_P = Fr::inv(Fr::from_u64(P));
+    fe_t wk = Fr::one();                                       // winv^k
+    for (uint32_t k = 0; k < P && k < n_out; ++k) {
+        fe_t acc = Fr::zero(), x = Fr::one();
+        for (uint32_t p = 0; p < P; ++p) { acc = Fr::add(acc, Fr::mul(val[p], x)); x = Fr::mul(x, wk); }
+        out[k] = Fr::mul(acc, inv_P);
+        wk = Fr::mul(wk, winv);
+    }
+}
+
+// The gates at row 0 in ONE launch, one workgroup per (point, gate) (the hoisting form of the leaf kernels), and one D2H.
+// fold = false: on the trace W_dev[0] (compute_F, evaluate_e).  fold = true: on the fold of the J traces at each of compute_G's
+// evaluation points -- the integers 0 .. d_G with one incoming trace, else the points_G roots of unity, the per-point challenges
+// folded with L_j(X_p).  X = 1 is one of the points on both routes and the fold there IS W_dev[0]: out.one_at.
+int pg_row0_values(Structure *S, bool fold, const fe_t *const *W_dev, const fe_t *const *challenges_host, size_t n_ch, size_t J, hipStream_t st,
+                   PgRow0 &out, std::string &err) {
+    if (S->field != 0) { err = "ProtoGalaxy polynomials need the 2-adic field bn256::Fr"; return 4; }
+    if (J == 0 || J > JMAX) { err = "unsupported number of traces"; return 4; }
+    PgSizes sz;
+    if (!pg_sizes(S, fold ? J - 1 : 1, sz)) { err = "structure has no gates"; return 4; }
+    FieldOps f{0};
+    const bool g_int = fold && J == 2 && tuning::get_or(tuning::PG_G_FFT, 0) == 0;
+    const uint32_t P = !fold ? 1u : (g_int ? (uint32_t)S->max_gate_degree + 1 : (uint32_t)sz.points_G);
+    const uint32_t n_gates = (uint32_t)S->gate_progs.size();
+    out.P = P;
+    out.g_int = g_int;
+    out.one_at = g_int ? 1u : 0u;                              // integer nodes 0, 1, ..; roots of unity w^0 = 1, w, ..
+    std::vector<fe_t> wcoef;                                   // [P][J] = L_j(X_p)   (FoldedWitness::new, folded_witness.rs:20-47)
+    std::vector<std::vector<fe_t>> ch_pt(P, std::vector<fe_t>(n_ch ? n_ch : 1, Fr::zero()));
+    if (fold) {
+        wcoef.resize((size_t)P * J);
+        const fe_t w = g_int ? Fr::one() : ntt::omega(ilog2(P), false);
+        fe_t x = g_int ? Fr::zero() : Fr::one();
+        for (uint32_t p = 0; p < P; ++p) {
+            // integer-point G folds the witnesses by halvings in the kernel: L_j(X_p) is only needed to fold challenges
+            if (!g_int || n_ch) {
+                std::vector<fe_t> L = lagrange_eval(x, (uint32_t)sz.lagrange_domain);
+                for (size_t j = 0; j < J; ++j) {
+                    wcoef[(size_t)p * J + j] = L[j];
+                    for (size_t c = 0; c < n_ch; ++c)         // fold_plonk_challenges :142-180
+                        ch_pt[p][c] = Fr::add(ch_pt[p][c], Fr::mul(challenges_host[j][c], L[j]));
+                }
+            }
+            x = g_int ? Fr::add(x, Fr::one()) : Fr::mul(x, w);
+        }
+    } else {
+        for (size_t c = 0; c < n_ch; ++c) ch_pt[0][c] = challenges_host[0][c];
+    }
+    // the specialised gate set in sweep form (k_pg_leaves_sweep<.., COMPAT>, hoist_mode 1) where the leaf route takes it, else the interpreter
+    const bool sweep = S->pg_spec_id >= 0 && S->k >= 10 && (!fold || g_int) && P <= DMAX + 1;
+    const uint32_t lpt = 8;                                    // the sweep kernel reads its table at slot lpt
+    uint32_t max_slots = 1;
+    std::vector<GateProg> gp(n_gates);
+    std::vector<fe_t> utab;
+    for (uint32_t g = 0; g < n_gates; ++g) {
+        Program &p = S->gate_progs[g];
+        max_slots = std::max(max_slots, p.nslots);
+        const size_t nu = p.uops.size() ? p.uops.size() : 1;
+        gp[g].prog = p.d_insns;
+        gp[g].n_insn = (uint32_t)p.insns.size();
+        gp[g].result = p.result;
+        gp[g].n_uniform = (uint32_t)nu;
+        gp[g].utab_off = (uint32_t)utab.size();
+        utab.resize(utab.size() + nu * P * (sweep ? lpt + 1 : 1u));
+        fe_t *tab = utab.data() + gp[g].utab_off;
+        for (uint32_t lp = 0; lp < P; ++lp)
+            if (!eval_uniform(p, f, ch_pt[lp].data(), n_ch, 0, false, 0, tab + (size_t)lp * nu, err)) return 7;
+        if (sweep) std::memcpy(tab + (size_t)lpt * P * nu, tab, (size_t)P * nu * sizeof(fe_t));      // the term coefficients as they are: no weight
+    }
+    if (max_slots > 32) { err = "row program needs more than 32 live registers"; return 4; }
+    Arena &A = S->arena;
+    A.reserve(Arena::pad((wcoef.size() + 1) * sizeof(fe_t)) + Arena::pad((utab.size() + 1) * sizeof(fe_t)) + Arena::pad(gp.size() * sizeof(GateProg)) +
+              Arena::pad(((size_t)n_gates * P + 1) * sizeof(fe_t)) + 4096);
+    A.reset();
+    fe_t *d_coef = A.take<fe_t>(wcoef.size() + 1);
+    fe_t *d_utab = A.take<fe_t>(utab.size() + 1);
+    GateProg *d_gp = A.take<GateProg>(gp.size());
+    fe_t *d_vals = A.take<fe_t>((size_t)n_gates * P + 1);
+    if (fold && !g_int) SRS_HIP_CHECK(hipMemcpyAsync(d_coef, wcoef.data(), wcoef.size() * sizeof(fe_t), hipMemcpyHostToDevice, st));
+    SRS_HIP_CHECK(hipMemcpyAsync(d_utab, utab.data(), utab.size() * sizeof(fe_t), hipMemcpyHostToDevice, st));
+    SRS_HIP_CHECK(hipMemcpyAsync(d_gp, gp.data(), gp.size() * sizeof(GateProg), hipMemcpyHostToDevice, st));
+    PgArgs a;
+    a.gates = d_gp;
+    a.n_gates = n_gates;
+    a.log_rows = S->k;
+    a.ctx.rows = (uint32_t)S->rows;
+    a.ctx.sel = S->d_sel_ptrs;
+    a.ctx.fix = S->d_fix_ptrs;
+    for (uint32_t j = 0; j < JMAX; ++j) a.ctx.W[j] = j < J ? W_dev[j] : nullptr;
+    a.ctx.J = (uint32_t)(fold ? J : 1);
+    a.ctx.wcoef = (fold && !g_int) ? d_coef : nullptr;
+    a.ctx.half = g_int ? 1u : 0u;
+    a.ctx.shard_rank = 0;
+    a.ctx.shard_world = 1;
+    a.ctx.local_rows = a.ctx.rows;
+    a.ctx.pt0 = 0;
+    a.compat = 1;
+    a.leaf_pts = P;
+    a.P = P;
+    a.utab = d_utab;
+    a.weights = nullptr;
+    a.wpts = 1;
+    a.tile_log = S->k >= 10 ? 10u : std::min<uint32_t>(7, S->k);
+    a.partial = nullptr;
+    a.shard_rank = 0;
+    a.shard_world = 1;
+    a.hoist = d_vals;
+    a.hoist_mode = 1;
+    const uint32_t threads = (1u << a.tile_log) / (S->k >= 10 ? 8u : 1u);
+    {
+        prof::Scope ps("pg_row0", st, (size_t)n_gates * P);
+        if (sweep) launch_pg_spec(S->pg_spec_id, a, P, n_gates, threads, st, true);
+        else if (max_slots <= 8) launch_pg_leaves<8>(a, P, n_gates, threads, 1, st);
+        else if (max_slots <= 12) launch_pg_leaves<12>(a, P, n_gates, threads, 1, st);
+        else if (max_slots <= 16) launch_pg_leaves<16>(a, P, n_gates, threads, 1, st);
+        else launch_pg_leaves<32>(a, P, n_gates, threads, 1, st);
+    }
+    out.vals.resize((size_t)n_gates * P);
+    SRS_HIP_CHECK(hipMemcpyAsync(out.vals.data(), d_vals, out.vals.size() * sizeof(fe_t), hipMemcpyDeviceToHost, st));
+    SRS_HIP_CHECK(hipStreamSynchronize(st));
+    SRS_HIP_CHECK(hipGetLastError());
+    prof::collect();
+    return 0;
+}
+
+bool pg_closed_route(int compat) { return compat && tuning::get_or(tuning::PG_COMPAT_TREE, 0) == 0; }
+
 // mode 0: compute_F, 1: compute_G, 2: evaluate_e.  W_dev: J device witness pointers (J = 1 for F / e).
 // challenges_host: J arrays of n_ch challenges.  weights_in: betas (F, e) / betas_stroke (G), betas_count values.
 // out_host: points_F / points_G coefficients (after ifft) or the single value e.
@@ -1202,6 +1400,21 @@ int pg_sum(Structure *S, int mode, const fe_t *const *W_dev, const fe_t *const *
     if (n_weights < sz.betas_count) { err = "not enough betas"; return 4; }
     FieldOps f{0};
     const uint32_t P_out = mode == 0 ? (uint32_t)sz.points_F : (mode == 1 ? (uint32_t)sz.points_G : 1u);
+    if (pg_closed_route(compat)) {
+        // the reference's leaf rows: the gates at row 0 from the device, the sums in closed form on the host.  A row-sharded structure has
+        // nothing to shard here (every rank holds row 0): rank 0 returns the whole polynomial, the others the zero polynomial
+        for (uint32_t m = 0; m < P_out; ++m) out_host[m] = Fr::zero();
+        *n_out = P_out;
+        if (S->shard_world > 1 && S->shard_rank != 0) return 0;
+        PgRow0 r0;
+        const int rc = pg_row0_values(S, mode == 1, W_dev, challenges_host, n_ch, J, st, r0, err);
+        if (rc) return rc;
+        const uint32_t n_gates = (uint32_t)S->gate_progs.size(), levels = (uint32_t)sz.betas_count;
+        if (mode == 0) pg_closed_F(r0.vals.data(), n_gates, S->k, weights_in, *delta, levels, out_host, P_out);
+        else if (mode == 1) pg_closed_G(S, r0, weights_in, levels, out_host, P_out);
+        else out_host[0] = pg_closed_sum(r0.vals.data(), 1, n_gates, S->k, weights_in, levels);
+        return 0;
+    }
     // compute_G with one incoming trace (L = 1, Lagrange domain {1, -1}): the folded witness L_0(X) w_0 + L_1(X) w_1 =
     // (w_0 + w_1)/2 + X (w_0 - w_1)/2 is LINEAR in X, so G has degree <= max gate degree d_G.  Instead of the reference's
     // next_pow2(d_G + 1) roots of unity (2 multiplies per advice load to fold the witness, then an ifft) G is evaluated at
@@ -1735,6 +1948,22 @@ int pg_K_from_G_device(Structure *S, const PgGValues &g, const fe_t &f_alpha, si
     return 0;
 }
 
+// the same from HOST values of G at the integer nodes 0 .. n - 1 (the closed-form compute_G): one small H2D in front
+int pg_K_from_G_values(Structure *S, const fe_t *vals_host, uint32_t n, const fe_t &f_alpha, size_t instances_to_fold, uint32_t log_domain_K,
+                       hipStream_t st, fe_t *out_host, std::string &err) {
+    static thread_local ThreadArena scratch;
+    scratch.reserve(Arena::pad((size_t)n * sizeof(fe_t)) + 256);
+    scratch.reset();
+    fe_t *d_vals = scratch.take<fe_t>(n);
+    SRS_HIP_CHECK(hipMemcpyAsync(d_vals, vals_host, (size_t)n * sizeof(fe_t), hipMemcpyHostToDevice, st));
+    PgGValues g;
+    g.vals_dev = d_vals;
+    g.n_dev = n;
+    g.degree = n - 1;
+    g.skip_one = false;
+    return pg_K_from_G_device(S, g, f_alpha, instances_to_fold, log_domain_K, st, out_host, err);     // synchronises: vals_host may go
+}
+
 size_t count_mismatch(const fe_t *a_dev, const fe_t *b_dev, size_t n, hipStream_t st) {
     if (!n) return 0;
     uint32_t *d = nullptr, h = 0;
@@ -1877,10 +2106,3 @@ int lincomb_rows(int field, fe_t *out, const fe_t *const *w_dev, const fe_t *coe
 
 }  // namespace rowprog
 }  // namespace srs
-
-#if defined(SRS_EMU) && !defined(SRS_EMU_ROWPROG_COMPILE_O)
-// Transition only.  tests/emu/Makefile builds rowprog_compile.hip as its own object and defines the macro above.  An emulator
-// Makefile that names its objects one by one and predates that object (the previous commit's) still links a loadable library,
-// because the compiler then rides in this object.  Delete this block with the next change of this file.
-#include "rowprog_compile.hip"
-#endif

@@ -1,6 +1,7 @@
 """One step of bench.py as a compact timeline, from a rocprofv3 --kernel-trace [--memory-copy-trace] CSV pair.
 usage: python tools/step_trace.py <kernel_trace.csv> [<memory_copy_trace.csv>] [step_from_end=2]
-A step starts at a k_pg_F_leaves launch (ProtoGalaxy::prove opens every CycleFold step).  Prints, per kernel of that step: start offset,
+A step starts at ProtoGalaxy::prove's first launch, which opens every CycleFold step: k_pg_F_leaves on the weighted-tree route, else the
+one k_pg_leaves_sweep launch that evaluates the gates at row 0 (the closed form of the reference's leaf rows).  Prints, per kernel of that step: start offset,
 duration, the idle gap before it (us), plus the copies' spans; then totals per kernel name."""
 import collections
 import csv
@@ -25,7 +26,8 @@ def main():
     ks = load(args[0], "Kernel_Name")
     cps = load(args[1], "Direction") if len(args) > 1 else []
     # (a prove may launch k_pg_F_leaves more than once back to back: a step starts at the first of a run)
-    starts = [i for i, k in enumerate(ks) if "k_pg_F_leaves" in k[2] and (i == 0 or "k_pg_F_leaves" not in ks[i - 1][2])]
+    first = "k_pg_F_leaves" if any("k_pg_F_leaves" in k[2] for k in ks) else "k_pg_leaves_sweep"
+    starts = [i for i, k in enumerate(ks) if first in k[2] and (i == 0 or first not in ks[i - 1][2])]
     a, b = starts[-back - 1], starts[-back]
     t0 = ks[a][0]
     t1 = ks[b][0]
