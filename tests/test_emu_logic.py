@@ -202,6 +202,58 @@ def test_emu_batch_invert_assigned(emu, oracle):
     _assigned_case(emu, oracle, 1, 1)
 
 
+# The CPU twins of the adversarial lookup inputs (tests/lookup_edge_cases.py) at their smallest sizes.  The emulator runs threads one
+# after another: these check the probing, comparing and 1/0 logic; the atomics are the GPU tests' business.
+def test_emu_m_probe_chains_from_the_last_slot(emu, oracle):
+    from lookup_edge_cases import collision_case
+    for field in (0, 1):
+        collision_case(emu, oracle, field, 5)
+
+
+def test_emu_m_keys_differ_in_one_limb(emu, oracle):
+    from lookup_edge_cases import limb_case
+    for field in (0, 1):
+        limb_case(emu, oracle, field)
+
+
+def test_emu_m_contended_slots(emu, oracle):
+    from lookup_edge_cases import contention_case
+    for field in (0, 1):
+        contention_case(emu, oracle, field, 6)
+
+
+def test_emu_hg_zero_denominators(emu, oracle):
+    from lookup_edge_cases import hg_challenges, hg_edge_case
+    for field in (0, 1):
+        for n in (1, 129, 1025):
+            for r in hg_challenges(field):
+                hg_edge_case(emu, oracle, field, n, r)
+
+
+def test_emu_batch_invert_assigned_zero_chunks(emu, oracle):
+    from lookup_edge_cases import assigned_edge_case
+    for field in (0, 1):
+        assigned_edge_case(emu, oracle, field)
+
+
+def test_emu_log_derivative_counts_violated_lookups(emu, oracle):
+    from lookup_edge_cases import log_derivative_count_case
+    for field in (0, 1):
+        log_derivative_count_case(emu, oracle, field)
+
+
+def test_emu_lookups_over_fq(emu, oracle):
+    from lookup_cases import run_lookup_case
+    run_lookup_case(emu, oracle, "scalar", 6, field=1)
+
+
+def test_emu_ntt_batch(emu, oracle):
+    from test_ntt_gpu import BATCH_CASES, ntt_batch_argument_checks, ntt_batch_case
+    for bits, k, stride, batch in BATCH_CASES[:5]:
+        ntt_batch_case(emu, oracle, bits, k, stride, batch)
+    ntt_batch_argument_checks(emu, oracle)
+
+
 def test_emu_two_pass_scatter():
     """tuning msm_sort = 2 (the two-pass scatter of large MSMs incl. the XCD-aware tile mapping) on a small MSM, on the emulator."""
     import sys

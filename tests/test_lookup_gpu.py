@@ -82,3 +82,63 @@ def test_batch_invert_assigned(srs, oracle):
     _assigned_case(srs, oracle, 0, 5000)
     _assigned_case(srs, oracle, 1, 1)
     _assigned_case(srs, oracle, 1, 1025)
+
+
+# ---- adversarial inputs (tests/lookup_edge_cases.py): what the small-integer tables above never feed the kernels
+@pytest.mark.parametrize("field", [0, 1])
+@pytest.mark.parametrize("k", [5, 10])
+def test_m_probe_chains_from_the_last_slot(srs, oracle, field, k):
+    """Every key hashes to the last slot: chains of rows / 2 that wrap to slot 0, absent looked-up values, repeats in another workgroup."""
+    from lookup_edge_cases import collision_case
+    collision_case(srs, oracle, field, k)
+
+
+def test_m_probe_chains_device_resident(srs, oracle):
+    from lookup_edge_cases import collision_case
+    collision_case(srs, oracle, 0, 10, device=True)
+
+
+@pytest.mark.parametrize("field", [0, 1])
+def test_m_keys_differ_in_one_limb(srs, oracle, field):
+    from lookup_edge_cases import limb_case
+    limb_case(srs, oracle, field)
+
+
+@pytest.mark.parametrize("field", [0, 1])
+def test_m_contended_slots(srs, oracle, field):
+    from lookup_edge_cases import contention_case
+    contention_case(srs, oracle, field, 10)
+
+
+@pytest.mark.parametrize("field", [0, 1])
+@pytest.mark.parametrize("n", [1, 127, 129, 1023, 1025, 2049])
+def test_hg_zero_denominators(srs, oracle, field, n):
+    """1/0 := 0 in h and in g, for r in {0, 1, p - 1, 0x1234567}."""
+    from lookup_edge_cases import HG_SIZES, hg_challenges, hg_edge_case
+    assert n in HG_SIZES
+    for r in hg_challenges(field):
+        hg_edge_case(srs, oracle, field, n, r)
+
+
+def test_hg_zero_denominators_device_resident(srs, oracle):
+    from lookup_edge_cases import hg_challenges, hg_edge_case
+    for field in (0, 1):
+        for r in hg_challenges(field):
+            hg_edge_case(srs, oracle, field, 2049, r, device=True)
+
+
+@pytest.mark.parametrize("field", [0, 1])
+def test_batch_invert_assigned_zero_chunks(srs, oracle, field):
+    from lookup_edge_cases import assigned_edge_case
+    assigned_edge_case(srs, oracle, field)
+
+
+@pytest.mark.parametrize("field", [0, 1])
+def test_log_derivative_counts_violated_lookups(srs, oracle, field):
+    from lookup_edge_cases import log_derivative_count_case
+    log_derivative_count_case(srs, oracle, field)
+
+
+def test_lookups_over_fq(srs, oracle):
+    run_lookup_case(srs, oracle, "scalar", 6, field=1)
+    run_lookup_case(srs, oracle, "vector", 5, field=1)

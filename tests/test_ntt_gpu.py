@@ -161,3 +161,67 @@ def test_ntt_asserts(srs):
         srs.fft.fft(np.zeros((12, 4), np.uint64))
     with pytest.raises(srs.fft.NotPowerOfTwo):
         srs.fft.ifft(np.zeros((0, 4), np.uint64))
+
+
+# (max radix bits, k, stride, batch): single workgroup with stride == n and stride > n; two passes; three passes; odd widths; four passes
+BATCH_CASES = ((8, 3, 8, 5), (8, 5, 40, 3), (8, 10, 1027, 2), (8, 11, 2056, 3), (4, 12, 4096, 2), (5, 15, (1 << 15) + 8, 2), (4, 16, 1 << 16, 2))
+_TRANSFORMS = {"fft": (0, 0), "ifft": (1, 0), "coset_fft": (0, 1), "coset_ifft": (1, 1)}
+
+
+def _ntt_batch(S, buf, n, stride, batch, fn, device=False):
+    """srs_ntt_batch on a copy of `buf` (host words, or the same words in device memory) -> (return code, the buffer afterwards)"""
+    from sirius_amd import _lib
+    from sirius_amd.commitment import _stream
+    inverse, coset = _TRANSFORMS[fn]
+    if device:
+        import torch
+        d = torch.from_numpy(buf.view(np.int64)).cuda()
+        rc = _lib.lib().srs_ntt_batch(_lib.FIELD_FR, d.data_ptr(), n, stride, batch, inverse, coset, _lib.SPACE_DEVICE, _stream())
+        return rc, d.cpu().numpy().view(np.uint64)
+    a = buf.copy()
+    rc = _lib.lib().srs_ntt_batch(_lib.FIELD_FR, a.ctypes.data, n, stride, batch, inverse, coset, _lib.SPACE_HOST, _stream())
+    return rc, a
+
+
+def ntt_batch_case(S, O, bits, k, stride, batch, device=False):
+    """`batch` vectors of 2^k words, `stride` apart: each becomes the oracle's transform of that vector alone, the words between them stay"""
+    from sirius_amd import _lib
+    n = 1 << k
+    buf = _rand(O, (batch - 1) * stride + n, 500 + k + batch)
+    gap = np.ones(buf.shape[0], bool)
+    for b in range(batch):
+        gap[b * stride:b * stride + n] = False
+    assert int(gap.sum()) == (batch - 1) * (stride - n)
+    try:
+        assert _lib.lib().srs_ntt_set_max_radix_bits(bits) == bits
+        for fn in FNS:
+            rc, got = _ntt_batch(S, buf, n, stride, batch, fn, device)
+            assert rc == _lib.OK, (fn, rc)
+            for b in range(batch):
+                v = buf[b * stride:b * stride + n]
+                assert np.array_equal(got[b * stride:b * stride + n], getattr(O, fn)(v)), (bits, k, stride, batch, fn, b)
+            assert np.array_equal(got[gap], buf[gap]), (bits, k, stride, batch, fn)
+    finally:
+        _lib.lib().srs_ntt_set_max_radix_bits(8)
+
+
+def ntt_batch_argument_checks(S, O, device=False):
+    from sirius_amd import _lib
+    buf = _rand(O, 64, 9)
+    for n, stride, batch, want in ((16, 15, 2, _lib.ERR_INVALID), (16, 0, 2, _lib.ERR_INVALID), (16, 16, 0, _lib.OK), (16, 3, 0, _lib.OK),
+                                   (12, 16, 2, _lib.ERR_NOT_POW2)):
+        for fn in ("fft", "coset_ifft"):
+            rc, got = _ntt_batch(S, buf, n, stride, batch, fn, device)
+            assert rc == want, (n, stride, batch, rc)
+            assert np.array_equal(got, buf), (n, stride, batch)
+
+
+@pytest.mark.parametrize("device", [False, True], ids=["host", "device"])
+@pytest.mark.parametrize("bits,k,stride,batch", BATCH_CASES)
+def test_ntt_batch_vs_oracle(srs, oracle, bits, k, stride, batch, device):
+    ntt_batch_case(srs, oracle, bits, k, stride, batch, device)
+
+
+@pytest.mark.parametrize("device", [False, True], ids=["host", "device"])
+def test_ntt_batch_argument_checks(srs, oracle, device):
+    ntt_batch_argument_checks(srs, oracle, device)
