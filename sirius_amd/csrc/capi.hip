@@ -264,6 +264,18 @@ int guarded(Fn &&fn) {
     }
 }
 
+int too_long_input(size_t n, const srs_ck *ck) {
+    return fail(SRS_ERR_TOO_LONG_INPUT, "Can't commit too long input: input len: " + std::to_string(n) + ", but limit is " +
+                                            std::to_string(ck->key.global_len));
+}
+
+// fn(key, shard) on the keys of a handle: its own (shard == nullptr), or the key of every shard of a multi-device handle
+template <class Fn>
+void for_each_key(const srs_ck *ck, Fn &&fn) {
+    if (ck->shards.empty()) fn(ck->key, static_cast<const CkShard *>(nullptr));
+    for (const auto &sh : ck->shards) fn(sh->key, sh.get());
+}
+
 bool valid_curve(int c) { return c == SRS_CURVE_BN256 || c == SRS_CURVE_GRUMPKIN; }
 bool valid_field(int f) { return f == SRS_FIELD_FR || f == SRS_FIELD_FQ; }
 
@@ -286,9 +298,92 @@ void to_affine_batch_t(const xyzz_t *in, affine_t *out, size_t n) {
         out[i].y = F::mul(in[i].y, F::mul(d, in[i].zz));
     }
 }
-void to_affine_batch(int curve, const xyzz_t *in, affine_t *out, size_t n) {
-    if (curve == SRS_CURVE_BN256) to_affine_batch_t<Bn256>(in, out, n); else to_affine_batch_t<Grumpkin>(in, out, n);
+// the one curve dispatch: go(tag), tag a Bn256 or a Grumpkin value
+template <class Go>
+decltype(auto) with_curve(int curve, Go &&go) {
+    return curve == SRS_CURVE_BN256 ? go(Bn256{}) : go(Grumpkin{});
 }
+// `batch` XYZZ sums, normalised, into the caller's srs_affine array: how every commit ends
+void store_affine(int curve, const xyzz_t *sums, size_t batch, srs_affine *out) {
+    std::vector<affine_t> aff(batch);
+    with_curve(curve, [&](auto tag) { to_affine_batch_t<decltype(tag)>(sums, aff.data(), batch); });
+    std::memcpy(out, aff.data(), batch * sizeof(affine_t));
+}
+
+// ---- host operands ------------------------------------------------------------------------------------------------
+// An entry with a `space` argument lists its operands ONCE, in the walk it hands to place(): inputs (in), outputs (out; out_into: an
+// output that lands in the staged buffer of an input, the in-place forms) and device-only temporaries (temp).  With device operands an
+// input or output IS the caller's pointer and only temporaries are allocated.  With host operands every one gets a device buffer from the
+// arena, inputs are copied up on the stream as they are placed, and close() copies every output back and synchronises the stream once.
+// place() runs the walk twice -- a first time to add up what the second time takes -- so the arena is grown at most once per call,
+// before its first take (growing frees what was handed out), and the reserve cannot disagree with the takes; an operand of zero
+// elements still gets a (one-byte) buffer of its own.  A_t: Arena, or ThreadArena, whose own reserve() follows its thread to another device.
+template <class A_t>
+class Staging {
+public:
+    Staging(A_t &arena, hipStream_t st, bool host) : A(arena), st(st), host(host) {}
+    template <class Walk>
+    void place(Walk walk) {
+        walk();
+        const size_t total = need;
+        if (!total) return;                      // device operands, no temporaries: the arena is not touched
+        A.reserve(total);
+        A.reset();
+        placing = true;
+        walk();
+        if (A.used != total) {
+            set_error("internal: staging: the two walks over the operands disagree");
+            throw DeviceError{5};
+        }
+    }
+    template <class T>
+    const T *in(const T *p, size_t n) {
+        if (!host) return p;
+        T *d = buffer<T>(n);
+        if (d && n) SRS_HIP_CHECK(hipMemcpyAsync(d, p, n * sizeof(T), hipMemcpyHostToDevice, st));
+        return d;
+    }
+    template <class T>
+    T *out(T *p, size_t n) {
+        return host ? out_into(p, buffer<T>(n), n) : p;
+    }
+    template <class T>
+    T *out_into(T *p, const T *staged_input, size_t n) {
+        if (!host) return p;
+        if (placing && n) outs.push_back(Out{p, staged_input, n * sizeof(T)});
+        return const_cast<T *>(staged_input);
+    }
+    template <class T>
+    T *temp(size_t n) { return buffer<T>(n); }
+    void close() {
+        if (!host) return;
+        for (const Out &o : outs) SRS_HIP_CHECK(hipMemcpyAsync(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost, st));
+        SRS_HIP_CHECK(hipStreamSynchronize(st));
+    }
+
+private:
+    struct Out {
+        void *host;
+        const void *dev;
+        size_t bytes;
+    };
+    template <class T>
+    T *buffer(size_t n) {
+        const size_t bytes = n ? n * sizeof(T) : 1;
+        if (placing) return reinterpret_cast<T *>(A.template take<char>(bytes));
+        need += Arena::pad(bytes);
+        return nullptr;
+    }
+    A_t &A;
+    hipStream_t st;
+    bool host, placing = false;
+    size_t need = 0;
+    std::vector<Out> outs;
+};
+// staging that does not outlive the call (a 2^24 NTT must not pin 512 MiB in a grow-only arena)
+struct ScopedArena : Arena {
+    ~ScopedArena() { release(); }
+};
 
 bool g_device_ok = false;
 int g_device = -1;        // the process's device (one process per GPU); bound by the first srs_init
@@ -344,13 +439,16 @@ size_t stripe_copy(Stripes sp, size_t a, size_t b, fe_t *dst, bool compact, cons
     return done;
 }
 
-template <class C>
-void sum_partials_t(const std::vector<std::vector<xyzz_t>> &parts, size_t batch, xyzz_t *out) {
-    for (size_t m = 0; m < batch; ++m) {
-        xyzz_t a = Ec<C>::identity();
-        for (const auto &p : parts) a = Ec<C>::add(a, p[m]);
-        out[m] = a;
-    }
+// out[m] = the sum over the shards d of parts[d * batch + m]
+void sum_partials(int curve, const xyzz_t *parts, size_t world, size_t batch, xyzz_t *out) {
+    with_curve(curve, [&](auto tag) {
+        using C = decltype(tag);
+        for (size_t m = 0; m < batch; ++m) {
+            xyzz_t a = Ec<C>::identity();
+            for (size_t d = 0; d < world; ++d) a = Ec<C>::add(a, parts[d * batch + m]);
+            out[m] = a;
+        }
+    });
 }
 
 // commit through a multi-device key: every shard thread stages ITS stripes of every vector on its device (from the caller's
@@ -359,7 +457,7 @@ void sum_partials_t(const std::vector<std::vector<xyzz_t>> &parts, size_t batch,
 int multi_commit(srs_ck *ck, const srs_fe *const *scalars, const size_t *n, size_t batch, int space, int repr, hipEvent_t ready,
                  xyzz_t *res) {
     const uint32_t world = (uint32_t)ck->shards.size();
-    std::vector<std::vector<xyzz_t>> parts(world, std::vector<xyzz_t>(batch));
+    std::vector<xyzz_t> parts((size_t)world * batch);
     for (uint32_t d = 0; d < world; ++d) {
         CkShard *sh = ck->shards[d].get();
         sh->post([=, &parts]() {
@@ -379,7 +477,7 @@ int multi_commit(srs_ck *ck, const srs_fe *const *scalars, const size_t *n, size
                             space == SRS_SPACE_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, sh->stream);
                 dptr[m] = dst;
             }
-            msm::run(sh->key, dptr.data(), nloc.data(), (uint32_t)batch, repr == SRS_REPR_MONT, sh->stream, parts[d].data());
+            msm::run(sh->key, dptr.data(), nloc.data(), (uint32_t)batch, repr == SRS_REPR_MONT, sh->stream, parts.data() + (size_t)d * batch);
         });
     }
     int rc = SRS_OK;
@@ -389,7 +487,7 @@ int multi_commit(srs_ck *ck, const srs_fe *const *scalars, const size_t *n, size
         if (r && !rc) { rc = r; err = ck->shards[d]->err; }
     }
     if (rc) return fail(rc, "multi-device commit: " + err);
-    if (ck->key.curve == SRS_CURVE_BN256) sum_partials_t<Bn256>(parts, batch, res); else sum_partials_t<Grumpkin>(parts, batch, res);
+    sum_partials(ck->key.curve, parts.data(), world, batch, res);
     return SRS_OK;
 }
 
@@ -501,19 +599,25 @@ int srs_tuning_get(const char *name, int64_t *value) {
 void srs_tuning_reset(void) { tuning::reset(); }
 const char *srs_tuning_name(int index) { return tuning::name_of(index); }
 
+// srs_init / srs_init_thread: makes device `dev` of `count` visible ones the calling thread's, if it is one the kernels are built for
+static int select_device(int dev, int count) {
+    if (dev >= count) return fail(SRS_ERR_INVALID, "device ordinal out of range");
+    SRS_HIP_CHECK(hipSetDevice(dev));
+    std::string arch;
+    if (!rt::device_arch(dev, arch)) return fail(SRS_ERR_DEVICE, "hipGetDeviceProperties failed");
+    if (arch.compare(0, 6, "gfx950") != 0)
+        return fail(SRS_ERR_DEVICE, "device is " + arch + ", kernels are built for gfx950 only");
+    return SRS_OK;
+}
+
 int srs_init(int device_ordinal) {
     return guarded([&]() -> int {
-        int count = 0;
-        if (hipGetDeviceCount(&count) != hipSuccess || count == 0)
-            return fail(SRS_ERR_DEVICE, "no HIP device visible: libsirius_amd has no CPU path");
+        const int count = physical_device_count();
+        if (count == 0) return fail(SRS_ERR_DEVICE, "no HIP device visible: libsirius_amd has no CPU path");
         int dev = device_ordinal;
         if (dev < 0) SRS_HIP_CHECK(hipGetDevice(&dev));
-        if (dev >= count) return fail(SRS_ERR_INVALID, "device ordinal out of range");
-        SRS_HIP_CHECK(hipSetDevice(dev));
-        std::string arch;
-        if (!rt::device_arch(dev, arch)) return fail(SRS_ERR_DEVICE, "hipGetDeviceProperties failed");
-        if (arch.compare(0, 6, "gfx950") != 0)
-            return fail(SRS_ERR_DEVICE, "device is " + arch + ", kernels are built for gfx950 only");
+        const int rc = select_device(dev, count);
+        if (rc) return rc;
         g_device = dev;
         g_device_ok = true;
         return SRS_OK;
@@ -522,19 +626,14 @@ int srs_init(int device_ordinal) {
 
 int srs_init_thread(int device_ordinal) {
     return guarded([&]() -> int {
-        int count = 0;
-        if (hipGetDeviceCount(&count) != hipSuccess || count == 0)
-            return fail(SRS_ERR_DEVICE, "no HIP device visible: libsirius_amd has no CPU path");
+        const int count = physical_device_count();
+        if (count == 0) return fail(SRS_ERR_DEVICE, "no HIP device visible: libsirius_amd has no CPU path");
         if (device_ordinal < 0) {            // unbind: back to the process's device
             t_device = -1;
             return SRS_OK;
         }
-        if (device_ordinal >= count) return fail(SRS_ERR_INVALID, "device ordinal out of range");
-        SRS_HIP_CHECK(hipSetDevice(device_ordinal));
-        std::string arch;
-        if (!rt::device_arch(device_ordinal, arch)) return fail(SRS_ERR_DEVICE, "hipGetDeviceProperties failed");
-        if (arch.compare(0, 6, "gfx950") != 0)
-            return fail(SRS_ERR_DEVICE, "device is " + arch + ", kernels are built for gfx950 only");
+        const int rc = select_device(device_ordinal, count);
+        if (rc) return rc;
         t_device = device_ordinal;
         return SRS_OK;
     });
@@ -686,19 +785,15 @@ int srs_ck_setup_synthetic(int curve, size_t len, uint64_t seed, uint32_t rank, 
     });
 }
 
+// the table lives in the multiplier's internal Montgomery form: window 0 converted back
 static int read_shard_bases(const msm::Key &key, hipStream_t st, srs_affine *out) {       // key.len points, this shard's window 0
     if (!key.len) return SRS_OK;
+    ScopedArena transient;
+    Staging z(transient, st, true);
     affine_t *tmp = nullptr;
-    SRS_HIP_CHECK(hipMalloc((void **)&tmp, key.len * sizeof(affine_t)));
-    try {
-        msm::read_bases(key, tmp, st);
-        SRS_HIP_CHECK(hipMemcpyAsync(out, tmp, key.len * sizeof(affine_t), hipMemcpyDeviceToHost, st));
-        SRS_HIP_CHECK(hipStreamSynchronize(st));
-    } catch (...) {
-        (void)hipFree(tmp);
-        throw;
-    }
-    (void)hipFree(tmp);
+    z.place([&] { tmp = z.out(reinterpret_cast<affine_t *>(out), key.len); });
+    msm::read_bases(key, tmp, st);
+    z.close();
     return SRS_OK;
 }
 
@@ -706,35 +801,21 @@ int srs_ck_get_bases(const srs_ck *ck, srs_affine *out) {
     if (!ck || ((ck->key.len || !ck->shards.empty()) && !out)) return fail(SRS_ERR_INVALID, "srs_ck_get_bases: bad argument");
     int rc = ensure_device();
     if (rc) return rc;
-    if (!ck->shards.empty()) {           // multi-device key: the whole key, stripes gathered from the shards
-        return guarded([&]() -> int {
-            const uint32_t world = (uint32_t)ck->shards.size();
-            for (uint32_t d = 0; d < world; ++d) {
-                CkShard *sh = ck->shards[d].get();
-                std::vector<srs_affine> loc(sh->key.len);
-                SRS_HIP_CHECK(hipSetDevice(sh->device));
-                read_shard_bases(sh->key, sh->stream, loc.data());
-                Stripes{d, world}.each_piece(0, ck->key.global_len, [&](size_t g, size_t l, size_t cnt) {
-                    std::memcpy(out + g, loc.data() + l, cnt * sizeof(srs_affine));
-                });
-            }
-            return ensure_device();
-        });
-    }
     return guarded([&]() -> int {
-        if (ck->key.len) {       // the table lives in the multiplier's internal Montgomery form: convert window 0 back
-            affine_t *tmp = nullptr;
-            SRS_HIP_CHECK(hipMalloc((void **)&tmp, ck->key.len * sizeof(affine_t)));
-            try {
-                msm::read_bases(ck->key, tmp, nullptr);
-                SRS_HIP_CHECK(hipMemcpy(out, tmp, ck->key.len * sizeof(affine_t), hipMemcpyDeviceToHost));
-            } catch (...) {
-                (void)hipFree(tmp);
-                throw;
+        for_each_key(ck, [&](const msm::Key &key, const CkShard *sh) {
+            if (!sh) {                       // the handle's own key: its key.len points
+                read_shard_bases(key, nullptr, out);
+                return;
             }
-            (void)hipFree(tmp);
-        }
-        return SRS_OK;
+            // multi-device key: the whole key, stripes gathered from the shards
+            std::vector<srs_affine> loc(key.len);
+            SRS_HIP_CHECK(hipSetDevice(sh->device));
+            read_shard_bases(key, sh->stream, loc.data());
+            Stripes{key.rank, key.world}.each_piece(0, key.global_len, [&](size_t g, size_t l, size_t cnt) {
+                std::memcpy(out + g, loc.data() + l, cnt * sizeof(srs_affine));
+            });
+        });
+        return ensure_device();
     });
 }
 size_t srs_ck_local_len(const srs_ck *ck) { return ck ? (ck->shards.empty() ? ck->key.len : ck->key.global_len) : 0; }
@@ -784,15 +865,11 @@ int srs_ck_count_off_curve(const srs_ck *ck, size_t *bad) {
     int rc = ensure_device();
     if (rc) return rc;
     return guarded([&]() -> int {
-        if (ck->shards.empty()) {
-            *bad = msm::count_off_curve(ck->key, nullptr);
-            return SRS_OK;
-        }
         size_t total = 0;
-        for (auto &sp : ck->shards) {
-            SRS_HIP_CHECK(hipSetDevice(sp->device));
-            total += msm::count_off_curve(sp->key, sp->stream);
-        }
+        for_each_key(ck, [&](const msm::Key &key, const CkShard *sh) {
+            if (sh) SRS_HIP_CHECK(hipSetDevice(sh->device));
+            total += msm::count_off_curve(key, sh ? sh->stream : nullptr);
+        });
         *bad = total;
         return ensure_device();
     });
@@ -829,14 +906,12 @@ int srs_ck_num_shards(const srs_ck *ck) { return ck ? (ck->shards.empty() ? 1 : 
 int srs_ck_msm_stats(const srs_ck *ck, uint64_t *out) {
     if (!ck || !out) return fail(SRS_ERR_INVALID, "srs_ck_msm_stats: bad argument");
     for (int i = 0; i < 4; ++i) out[i] = 0;
-    auto add = [&](const msm::Key &k) {
+    for_each_key(ck, [&](const msm::Key &k, const CkShard *) {
         out[0] += k.stat_slot_sets;
         out[1] += k.stat_hot_sets;
         out[2] += k.stat_redo;
         out[3] += k.stat_other_sets;
-    };
-    if (ck->shards.empty()) add(ck->key);
-    for (const auto &sh : ck->shards) add(sh->key);
+    });
     return SRS_OK;
 }
 
@@ -859,24 +934,25 @@ int srs_ck_shard_stats(const srs_ck *ck, int shard, uint64_t *out) {
 
 int srs_ck_has_wide_table(const srs_ck *ck) {
     if (!ck) return 0;
-    if (ck->shards.empty()) return ck->key.table_w != nullptr ? 1 : 0;
-    for (const auto &sh : ck->shards)
-        if (sh->key.len && !sh->key.table_w) return 0;
-    return 1;
+    int wide = 1;                            // every key has one; a shard without bases has nothing to tabulate and does not count
+    for_each_key(ck, [&](const msm::Key &k, const CkShard *sh) {
+        if ((k.len || !sh) && !k.table_w) wide = 0;
+    });
+    return wide;
 }
 
 int srs_ck_is_compact(const srs_ck *ck) {
     if (!ck) return 0;
-    if (ck->shards.empty()) return ck->key.compact ? 1 : 0;
-    for (const auto &sh : ck->shards)
-        if (!sh->key.compact) return 0;
-    return 1;
+    int compact = 1;                         // every key is, empty shards included (their form is decided too)
+    for_each_key(ck, [&](const msm::Key &k, const CkShard *) {
+        if (!k.compact) compact = 0;
+    });
+    return compact;
 }
 size_t srs_ck_table_bytes(const srs_ck *ck) {
     if (!ck) return 0;
-    if (ck->shards.empty()) return msm::table_bytes(ck->key);
     size_t total = 0;
-    for (const auto &sh : ck->shards) total += msm::table_bytes(sh->key);
+    for_each_key(ck, [&](const msm::Key &k, const CkShard *) { total += msm::table_bytes(k); });
     return total;
 }
 
@@ -892,7 +968,7 @@ int srs_glv_constants(int curve, srs_fe *lambda, srs_fe *beta) {
         std::memcpy(lambda, &l, 32);
         std::memcpy(beta, &b, 32);
     };
-    if (curve == SRS_CURVE_BN256) go(Bn256{}); else go(Grumpkin{});
+    with_curve(curve, go);
     return SRS_OK;
 }
 int srs_glv_decompose(int curve, const srs_fe *k, int repr, srs_fe *k1_abs, srs_fe *k2_abs, int *neg1, int *neg2) {
@@ -913,7 +989,7 @@ int srs_glv_decompose(int curve, const srs_fe *k, int repr, srs_fe *k1_abs, srs_
         *neg1 = g.neg1 ? 1 : 0;
         *neg2 = g.neg2 ? 1 : 0;
     };
-    if (curve == SRS_CURVE_BN256) go(Bn256{}); else go(Grumpkin{});
+    with_curve(curve, go);
     return SRS_OK;
 }
 
@@ -939,9 +1015,7 @@ int srs_commit_batch(srs_ck *ck, const srs_fe *const *scalars, const size_t *n, 
     if (batch == 0) return SRS_OK;
     std::lock_guard<std::recursive_mutex> key_lock(ck->mu);
     for (size_t m = 0; m < batch; ++m) {
-        if (n[m] > ck->key.global_len)
-            return fail(SRS_ERR_TOO_LONG_INPUT, "Can't commit too long input: input len: " + std::to_string(n[m]) +
-                                                    ", but limit is " + std::to_string(ck->key.global_len));
+        if (n[m] > ck->key.global_len) return too_long_input(n[m], ck);
         if (n[m] && !scalars[m]) return fail(SRS_ERR_INVALID, "srs_commit: null scalar vector");
     }
     int rc = ensure_device();
@@ -958,9 +1032,7 @@ int srs_commit_batch(srs_ck *ck, const srs_fe *const *scalars, const size_t *n, 
             std::vector<xyzz_t> res(batch);
             int mrc = multi_commit(ck, scalars, n, batch, space, repr, ready, res.data());
             if (mrc) return mrc;
-            std::vector<affine_t> aff(batch);
-            to_affine_batch(ck->key.curve, res.data(), aff.data(), batch);
-            std::memcpy(out, aff.data(), batch * sizeof(affine_t));
+            store_affine(ck->key.curve, res.data(), batch, out);
             return SRS_OK;
         });
     }
@@ -970,25 +1042,13 @@ int srs_commit_batch(srs_ck *ck, const srs_fe *const *scalars, const size_t *n, 
         std::vector<uint32_t> nloc(batch);
         std::vector<const fe_t *> dptr(batch);
         for (size_t m = 0; m < batch; ++m) nloc[m] = (uint32_t)Stripes{rank, world}.count(n[m]);
-        if (space == SRS_SPACE_DEVICE) {
-            for (size_t m = 0; m < batch; ++m) dptr[m] = reinterpret_cast<const fe_t *>(scalars[m]);
-        } else {
-            // stage the FULL vectors (the kernels pick this rank's stripes)
-            size_t total = 0;
-            for (size_t m = 0; m < batch; ++m) total += Arena::pad(n[m] * sizeof(fe_t));
-            ck->staging.reserve(total + 256);
-            ck->staging.reset();
-            for (size_t m = 0; m < batch; ++m) {
-                fe_t *d = ck->staging.take<fe_t>(n[m] ? n[m] : 1);
-                if (n[m]) SRS_HIP_CHECK(hipMemcpyAsync(d, scalars[m], n[m] * sizeof(fe_t), hipMemcpyHostToDevice, st));
-                dptr[m] = d;
-            }
-        }
+        Staging z(ck->staging, st, space != SRS_SPACE_DEVICE);
+        z.place([&] {                        // host scalars: the FULL vectors are staged (the kernels pick this rank's stripes)
+            for (size_t m = 0; m < batch; ++m) dptr[m] = z.in(reinterpret_cast<const fe_t *>(scalars[m]), n[m]);
+        });
         std::vector<xyzz_t> res(batch);
-        msm::run(ck->key, dptr.data(), nloc.data(), (uint32_t)batch, repr == SRS_REPR_MONT, st, res.data());
-        std::vector<affine_t> aff(batch);
-        to_affine_batch(ck->key.curve, res.data(), aff.data(), batch);
-        std::memcpy(out, aff.data(), batch * sizeof(affine_t));
+        msm::run(ck->key, dptr.data(), nloc.data(), (uint32_t)batch, repr == SRS_REPR_MONT, st, res.data());      // ends synchronised
+        store_affine(ck->key.curve, res.data(), batch, out);
         return SRS_OK;
     });
 }
@@ -1149,7 +1209,7 @@ int commit_streamed_core(StreamRes ck_, const std::vector<Seg> &segs, size_t n, 
         if (missed) acc = redo;
         *sum_out = acc;
     };
-    if (ck->key.curve == SRS_CURVE_BN256) go(Bn256{}); else go(Grumpkin{});
+    with_curve(ck->key.curve, go);
     ht.mark("host finish");
     prof::collect();
     ht.mark("prof");
@@ -1163,9 +1223,7 @@ int commit_streamed(srs_ck *ck, const std::vector<Seg> &segs, size_t n, const st
     StreamRes r{ck->key, ck->copy_stream, ck->events};
     int rc = commit_streamed_core(r, segs, n, cut, dst, repr, st, &sum);
     if (rc) return rc;
-    affine_t a;
-    to_affine_batch(ck->key.curve, &sum, &a, 1);
-    std::memcpy(out, &a, sizeof(a));
+    store_affine(ck->key.curve, &sum, 1, out);
     return SRS_OK;
 }
 
@@ -1292,21 +1350,15 @@ int multi_commit_streamed(srs_ck *ck, const std::vector<Seg> &segs, size_t n, fe
         if (!direct && sh->peer_done) SRS_HIP_CHECK(hipStreamWaitEvent(st, sh->peer_done, 0));   // the caller's stream sees the whole device copy
     }
     xyzz_t sum;
-    std::vector<std::vector<xyzz_t>> pv(world, std::vector<xyzz_t>(1));
-    for (uint32_t d = 0; d < world; ++d) pv[d][0] = parts[d];
-    if (ck->key.curve == SRS_CURVE_BN256) sum_partials_t<Bn256>(pv, 1, &sum); else sum_partials_t<Grumpkin>(pv, 1, &sum);
-    affine_t a;
-    to_affine_batch(ck->key.curve, &sum, &a, 1);
-    std::memcpy(out, &a, sizeof(a));
+    sum_partials(ck->key.curve, parts.data(), world, 1, &sum);
+    store_affine(ck->key.curve, &sum, 1, out);
     return SRS_OK;
 }
 }  // namespace
 
 int srs_commit_upload(srs_ck *ck, const srs_fe *scalars_host, size_t n, srs_fe *dev_copy, int repr, void *stream, srs_affine *out) {
     if (!ck || !out || (n && !scalars_host)) return fail(SRS_ERR_INVALID, "srs_commit_upload: bad argument");
-    if (n > ck->key.global_len)
-        return fail(SRS_ERR_TOO_LONG_INPUT, "Can't commit too long input: input len: " + std::to_string(n) + ", but limit is " +
-                                                std::to_string(ck->key.global_len));
+    if (n > ck->key.global_len) return too_long_input(n, ck);
     int rc = ensure_device();
     if (rc) return rc;
     std::lock_guard<std::recursive_mutex> key_lock(ck->mu);
@@ -1384,9 +1436,7 @@ int srs_commit_upload_columns(srs_ck *ck, const srs_fe *const *columns_host, con
                               srs_fe *dev_copy, int repr, void *stream, srs_affine *out) {
     if (!ck || !out || (n_columns && (!columns_host || !lens))) return fail(SRS_ERR_INVALID, "srs_commit_upload_columns: bad argument");
     const size_t n = srs_concat_len(lens, n_columns, pad_size);
-    if (n > ck->key.global_len)
-        return fail(SRS_ERR_TOO_LONG_INPUT, "Can't commit too long input: input len: " + std::to_string(n) + ", but limit is " +
-                                                std::to_string(ck->key.global_len));
+    if (n > ck->key.global_len) return too_long_input(n, ck);
     for (size_t c = 0; c < n_columns; ++c)
         if (lens[c] && !columns_host[c]) return fail(SRS_ERR_INVALID, "srs_commit_upload_columns: null column");
     int rc = ensure_device();
@@ -1439,7 +1489,7 @@ int srs_point_sum(int curve, const srs_affine *points, size_t n, srs_affine *out
         affine_t a = Ec<C>::to_affine(acc);
         std::memcpy(out, &a, sizeof(a));
     };
-    if (curve == SRS_CURVE_BN256) go(Bn256{}); else go(Grumpkin{});
+    with_curve(curve, go);
     return SRS_OK;
 }
 
@@ -1455,7 +1505,7 @@ int srs_point_mul(int curve, const srs_fe *scalar, int repr, const srs_affine *p
         affine_t a = Ec<C>::to_affine(Ec<C>::mul_canon(s.v, P));
         std::memcpy(out, &a, sizeof(a));
     };
-    if (curve == SRS_CURVE_BN256) go(Bn256{}); else go(Grumpkin{});
+    with_curve(curve, go);
     return SRS_OK;
 }
 
@@ -1474,24 +1524,15 @@ int srs_ntt_batch(int field, srs_fe *a, size_t n, size_t stride, size_t batch, i
     if (rc) return rc;
     return guarded([&]() -> int {
         hipStream_t st = (hipStream_t)stream;
-        if (space == SRS_SPACE_DEVICE) {
-            ntt::run(reinterpret_cast<fe_t *>(a), log_n, stride, (uint32_t)batch, inverse != 0, coset != 0, st);
-            SRS_HIP_CHECK(hipStreamSynchronize(st));
-        } else {
-            fe_t *d = nullptr;
-            size_t total = (batch - 1) * stride + n;
-            SRS_HIP_CHECK(hipMalloc((void **)&d, total * sizeof(fe_t)));
-            try {
-                SRS_HIP_CHECK(hipMemcpyAsync(d, a, total * sizeof(fe_t), hipMemcpyHostToDevice, st));
-                ntt::run(d, log_n, stride, (uint32_t)batch, inverse != 0, coset != 0, st);
-                SRS_HIP_CHECK(hipMemcpyAsync(a, d, total * sizeof(fe_t), hipMemcpyDeviceToHost, st));
-                SRS_HIP_CHECK(hipStreamSynchronize(st));
-            } catch (...) {
-                (void)hipFree(d);
-                throw;
-            }
-            SRS_HIP_CHECK(hipFree(d));
-        }
+        const bool host = space != SRS_SPACE_DEVICE;
+        const size_t total = (batch - 1) * stride + n;
+        ScopedArena transient;
+        Staging z(transient, st, host);
+        fe_t *d = nullptr;
+        z.place([&] { d = z.out_into(reinterpret_cast<fe_t *>(a), z.in(reinterpret_cast<const fe_t *>(a), total), total); });
+        ntt::run(d, log_n, stride, (uint32_t)batch, inverse != 0, coset != 0, st);
+        z.close();
+        if (!host) SRS_HIP_CHECK(hipStreamSynchronize(st));
         SRS_HIP_CHECK(hipGetLastError());
         return SRS_OK;
     });
@@ -1532,7 +1573,7 @@ static void point_lincomb_impl(int curve, const srs_affine *acc, const srs_affin
         affine_t r = Ec<C>::to_affine(a);
         std::memcpy(out, &r, sizeof(r));
     };
-    if (curve == SRS_CURVE_BN256) go(Bn256{}); else go(Grumpkin{});
+    with_curve(curve, go);
 }
 
 int srs_fe_powers(int field, const srs_fe *r, size_t n, srs_fe *out) {
@@ -1856,26 +1897,15 @@ static int cross_terms_impl(srs_structure *S, srs_ck *ck, const srs_fe *W1, cons
         rowprog::Structure *s = S->s;
         const size_t d = rowprog::degree(s), rows = rowprog::rows(s), wlen = rowprog::num_witness_columns(s) * rows;
         if (d == 0) return SRS_OK;
-        if (ck && rows > ck->key.global_len)
-            return fail(SRS_ERR_TOO_LONG_INPUT, "Can't commit too long input: input len: " + std::to_string(rows) +
-                                                    ", but limit is " + std::to_string(ck->key.global_len));
-        const bool host = space != SRS_SPACE_DEVICE;
-        const bool own_T = host || !T_out;
-        size_t need = 1024;
-        if (host) need += 2 * Arena::pad(wlen * sizeof(fe_t));
-        if (own_T) need += d * Arena::pad(rows * sizeof(fe_t));
-        S->io.reserve(need);
-        S->io.reset();
-        const fe_t *dW1 = reinterpret_cast<const fe_t *>(W1), *dW2 = reinterpret_cast<const fe_t *>(W2);
-        if (host) {
-            fe_t *a = S->io.take<fe_t>(wlen ? wlen : 1), *b = S->io.take<fe_t>(wlen ? wlen : 1);
-            SRS_HIP_CHECK(hipMemcpyAsync(a, W1, wlen * sizeof(fe_t), hipMemcpyHostToDevice, st));
-            SRS_HIP_CHECK(hipMemcpyAsync(b, W2, wlen * sizeof(fe_t), hipMemcpyHostToDevice, st));
-            dW1 = a;
-            dW2 = b;
-        }
+        if (ck && rows > ck->key.global_len) return too_long_input(rows, ck);
+        Staging z(S->io, st, space != SRS_SPACE_DEVICE);
+        const fe_t *dW1 = nullptr, *dW2 = nullptr;
         std::vector<fe_t *> dT(d);
-        for (size_t k = 0; k < d; ++k) dT[k] = own_T ? S->io.take<fe_t>(rows) : reinterpret_cast<fe_t *>(T_out[k]);
+        z.place([&] {                        // without T_out (commitments only) the T vectors are temporaries, in either space
+            dW1 = z.in(reinterpret_cast<const fe_t *>(W1), wlen);
+            dW2 = z.in(reinterpret_cast<const fe_t *>(W2), wlen);
+            for (size_t k = 0; k < d; ++k) dT[k] = T_out ? z.out(reinterpret_cast<fe_t *>(T_out[k]), rows) : z.temp<fe_t>(rows);
+        });
         if (rowprog::shard_world(s) > 1)                 // rows of the other ranks' stripes are not evaluated: they read as zero, in the
             for (size_t k = 0; k < d; ++k)               // library's staging and in caller-provided device vectors alike (the error fold
                 SRS_HIP_CHECK(hipMemsetAsync(dT[k], 0, rows * sizeof(fe_t), st));      // then leaves E unchanged outside the local stripes)
@@ -1890,10 +1920,7 @@ static int cross_terms_impl(srs_structure *S, srs_ck *ck, const srs_fe *W1, cons
             int crc = srs_commit_batch(ck, v.data(), nn.data(), d, SRS_SPACE_DEVICE, SRS_REPR_MONT, stream, commits_out);
             if (crc) return crc;
         }
-        if (host && T_out) {
-            for (size_t k = 0; k < d; ++k) SRS_HIP_CHECK(hipMemcpyAsync(T_out[k], dT[k], rows * sizeof(fe_t), hipMemcpyDeviceToHost, st));
-            SRS_HIP_CHECK(hipStreamSynchronize(st));
-        }
+        z.close();
         return SRS_OK;
     });
 }
@@ -1918,25 +1945,17 @@ int srs_eval_gates(srs_structure *S, int homogeneous, const srs_fe *W, const srs
         hipStream_t st = (hipStream_t)stream;
         rowprog::Structure *s = S->s;
         const size_t rows = rowprog::rows(s), wlen = rowprog::num_witness_columns(s) * rows;
-        const bool host = space != SRS_SPACE_DEVICE;
-        const fe_t *dW = reinterpret_cast<const fe_t *>(W);
-        fe_t *dO = reinterpret_cast<fe_t *>(out);
-        if (host) {
-            S->io.reserve(Arena::pad(wlen * sizeof(fe_t)) + Arena::pad(rows * sizeof(fe_t)) + 1024);
-            S->io.reset();
-            fe_t *a = S->io.take<fe_t>(wlen ? wlen : 1);
-            SRS_HIP_CHECK(hipMemcpyAsync(a, W, wlen * sizeof(fe_t), hipMemcpyHostToDevice, st));
-            dW = a;
-            dO = S->io.take<fe_t>(rows);
-        }
+        Staging z(S->io, st, space != SRS_SPACE_DEVICE);
+        const fe_t *dW = nullptr;
+        fe_t *outs[1] = {nullptr};
+        z.place([&] {
+            dW = z.in(reinterpret_cast<const fe_t *>(W), wlen);
+            outs[0] = z.out(reinterpret_cast<fe_t *>(out), rows);
+        });
         std::string err;
-        fe_t *outs[1] = {dO};
         int erc = rowprog::evaluate(s, homogeneous ? 2 : 1, dW, nullptr, reinterpret_cast<const fe_t *>(challenges), n_challenges, outs, st, err);
         if (erc) return fail(erc, "srs_eval_gates: " + err);
-        if (host) {
-            SRS_HIP_CHECK(hipMemcpyAsync(out, dO, rows * sizeof(fe_t), hipMemcpyDeviceToHost, st));
-            SRS_HIP_CHECK(hipStreamSynchronize(st));
-        }
+        z.close();
         return SRS_OK;
     });
 }
@@ -1951,26 +1970,18 @@ int srs_is_sat_gates(srs_structure *S, int homogeneous, const srs_fe *W, const s
         hipStream_t st = (hipStream_t)stream;
         rowprog::Structure *s = S->s;
         const size_t rows = rowprog::rows(s), wlen = rowprog::num_witness_columns(s) * rows;
-        const bool host = space != SRS_SPACE_DEVICE;
-        S->io.reserve(Arena::pad((wlen + 1) * sizeof(fe_t)) + 2 * Arena::pad(rows * sizeof(fe_t)) + 1024);
-        S->io.reset();
-        const fe_t *dW = reinterpret_cast<const fe_t *>(W), *dE = reinterpret_cast<const fe_t *>(E);
-        if (host) {
-            fe_t *a = S->io.take<fe_t>(wlen + 1);
-            SRS_HIP_CHECK(hipMemcpyAsync(a, W, wlen * sizeof(fe_t), hipMemcpyHostToDevice, st));
-            dW = a;
-            if (E) {
-                fe_t *e = S->io.take<fe_t>(rows);
-                SRS_HIP_CHECK(hipMemcpyAsync(e, E, rows * sizeof(fe_t), hipMemcpyHostToDevice, st));
-                dE = e;
-            }
-        }
-        fe_t *vals = S->io.take<fe_t>(rows);
-        fe_t *outs[1] = {vals};
+        Staging z(S->io, st, space != SRS_SPACE_DEVICE);
+        const fe_t *dW = nullptr, *dE = nullptr;
+        fe_t *outs[1] = {nullptr};
+        z.place([&] {
+            dW = z.in(reinterpret_cast<const fe_t *>(W), wlen);
+            if (E) dE = z.in(reinterpret_cast<const fe_t *>(E), rows);
+            outs[0] = z.temp<fe_t>(rows);
+        });
         std::string err;
         int erc = rowprog::evaluate(s, homogeneous ? 2 : 1, dW, nullptr, reinterpret_cast<const fe_t *>(challenges), n_challenges, outs, st, err);
         if (erc) return fail(erc, "srs_is_sat_gates: " + err);
-        *mismatch_count = rowprog::count_mismatch(vals, dE, rows, st);
+        *mismatch_count = rowprog::count_mismatch(outs[0], dE, rows, st);     // ends synchronised
         return SRS_OK;
     });
 }
@@ -2069,23 +2080,16 @@ static int sparse_apply(srs_sparse *M, const srs_fe *Z, int space, void *stream,
     return guarded([&]() -> int {
         hipStream_t st = (hipStream_t)stream;
         const size_t n = decider::dim(M->m);
-        const bool host = space != SRS_SPACE_DEVICE;
-        const fe_t *dZ = reinterpret_cast<const fe_t *>(Z);
-        fe_t *dY = reinterpret_cast<fe_t *>(y);
-        if (host) {
-            M->io.reserve(2 * Arena::pad((n + 1) * sizeof(fe_t)) + 1024);
-            M->io.reset();
-            fe_t *a = M->io.take<fe_t>(n + 1);
-            SRS_HIP_CHECK(hipMemcpyAsync(a, Z, n * sizeof(fe_t), hipMemcpyHostToDevice, st));
-            dZ = a;
-            if (y) dY = M->io.take<fe_t>(n + 1);
-        }
-        if (mismatch_count) *mismatch_count = decider::permutation_mismatches(M->m, dZ, st);
+        Staging z(M->io, st, space != SRS_SPACE_DEVICE);
+        const fe_t *dZ = nullptr;
+        fe_t *dY = nullptr;
+        z.place([&] {
+            dZ = z.in(reinterpret_cast<const fe_t *>(Z), n);
+            if (y) dY = z.out(reinterpret_cast<fe_t *>(y), n);
+        });
+        if (mismatch_count) *mismatch_count = decider::permutation_mismatches(M->m, dZ, st);      // ends synchronised
         else decider::matvec(M->m, dZ, dY, st);
-        if (host && y) {
-            SRS_HIP_CHECK(hipMemcpyAsync(y, dY, n * sizeof(fe_t), hipMemcpyDeviceToHost, st));
-            SRS_HIP_CHECK(hipStreamSynchronize(st));
-        }
+        z.close();
         return SRS_OK;
     });
 }
@@ -2131,34 +2135,23 @@ int srs_lookup_coeff_1(srs_structure *S, const srs_fe *advice, const srs_fe *r, 
         rowprog::Structure *s = S->s;
         const size_t L = rowprog::num_lookups(s), rows = rowprog::rows(s), alen = rowprog::num_advice(s) * rows;
         if (!L) return fail(SRS_ERR_INVALID, "srs_lookup_coeff_1: structure has no lookup arguments");
-        const bool host = space != SRS_SPACE_DEVICE;
+        Staging z(S->io, st, space != SRS_SPACE_DEVICE);
         std::vector<fe_t *> dl(L), dt(L), dm(L);
-        const fe_t *dA = reinterpret_cast<const fe_t *>(advice);
-        if (host) {
-            S->io.reserve(Arena::pad((alen + 1) * sizeof(fe_t)) + 3 * L * Arena::pad(rows * sizeof(fe_t)) + 1024);
-            S->io.reset();
-            fe_t *a = S->io.take<fe_t>(alen + 1);
-            SRS_HIP_CHECK(hipMemcpyAsync(a, advice, alen * sizeof(fe_t), hipMemcpyHostToDevice, st));
-            dA = a;
-            for (size_t i = 0; i < L; ++i) { dl[i] = S->io.take<fe_t>(rows); dt[i] = S->io.take<fe_t>(rows); dm[i] = S->io.take<fe_t>(rows); }
-        } else {
+        const fe_t *dA = nullptr;
+        z.place([&] {
+            dA = z.in(reinterpret_cast<const fe_t *>(advice), alen);
             for (size_t i = 0; i < L; ++i) {
-                dl[i] = reinterpret_cast<fe_t *>(ls[i]); dt[i] = reinterpret_cast<fe_t *>(ts[i]); dm[i] = reinterpret_cast<fe_t *>(ms[i]);
+                dl[i] = z.out(reinterpret_cast<fe_t *>(ls[i]), rows);
+                dt[i] = z.out(reinterpret_cast<fe_t *>(ts[i]), rows);
+                dm[i] = z.out(reinterpret_cast<fe_t *>(ms[i]), rows);
             }
-        }
+        });
         fe_t rr;
         std::memcpy(&rr, r, 32);
         std::string err;
         int erc = rowprog::lookup_coeff_1(s, dA, rr, dl.data(), dt.data(), dm.data(), st, err);
         if (erc) return fail(erc, "srs_lookup_coeff_1: " + err);
-        if (host) {
-            for (size_t i = 0; i < L; ++i) {
-                SRS_HIP_CHECK(hipMemcpyAsync(ls[i], dl[i], rows * sizeof(fe_t), hipMemcpyDeviceToHost, st));
-                SRS_HIP_CHECK(hipMemcpyAsync(ts[i], dt[i], rows * sizeof(fe_t), hipMemcpyDeviceToHost, st));
-                SRS_HIP_CHECK(hipMemcpyAsync(ms[i], dm[i], rows * sizeof(fe_t), hipMemcpyDeviceToHost, st));
-            }
-            SRS_HIP_CHECK(hipStreamSynchronize(st));
-        }
+        z.close();
         return SRS_OK;
     });
 }
@@ -2174,24 +2167,21 @@ int srs_lookup_coeff_2(int field, const srs_fe *l, const srs_fe *t, const srs_fe
         hipStream_t st = (hipStream_t)stream;
         fe_t rr;
         std::memcpy(&rr, r, 32);
-        if (space == SRS_SPACE_DEVICE) {
-            rowprog::lookup_coeff_2(field, reinterpret_cast<const fe_t *>(l), reinterpret_cast<const fe_t *>(t),
-                                    reinterpret_cast<const fe_t *>(m), rr, n, reinterpret_cast<fe_t *>(h), reinterpret_cast<fe_t *>(g), st);
-            SRS_HIP_CHECK(hipStreamSynchronize(st));
-        } else {
-            fe_t *buf = nullptr;
-            SRS_HIP_CHECK(hipMalloc((void **)&buf, 5 * n * sizeof(fe_t)));
-            try {
-                SRS_HIP_CHECK(hipMemcpyAsync(buf, l, n * sizeof(fe_t), hipMemcpyHostToDevice, st));
-                SRS_HIP_CHECK(hipMemcpyAsync(buf + n, t, n * sizeof(fe_t), hipMemcpyHostToDevice, st));
-                SRS_HIP_CHECK(hipMemcpyAsync(buf + 2 * n, m, n * sizeof(fe_t), hipMemcpyHostToDevice, st));
-                rowprog::lookup_coeff_2(field, buf, buf + n, buf + 2 * n, rr, n, buf + 3 * n, buf + 4 * n, st);
-                SRS_HIP_CHECK(hipMemcpyAsync(h, buf + 3 * n, n * sizeof(fe_t), hipMemcpyDeviceToHost, st));
-                SRS_HIP_CHECK(hipMemcpyAsync(g, buf + 4 * n, n * sizeof(fe_t), hipMemcpyDeviceToHost, st));
-                SRS_HIP_CHECK(hipStreamSynchronize(st));
-            } catch (...) { (void)hipFree(buf); throw; }
-            (void)hipFree(buf);
-        }
+        const bool host = space != SRS_SPACE_DEVICE;
+        ScopedArena transient;
+        Staging z(transient, st, host);
+        const fe_t *dl = nullptr, *dt = nullptr, *dm = nullptr;
+        fe_t *dh = nullptr, *dg = nullptr;
+        z.place([&] {
+            dl = z.in(reinterpret_cast<const fe_t *>(l), n);
+            dt = z.in(reinterpret_cast<const fe_t *>(t), n);
+            dm = z.in(reinterpret_cast<const fe_t *>(m), n);
+            dh = z.out(reinterpret_cast<fe_t *>(h), n);
+            dg = z.out(reinterpret_cast<fe_t *>(g), n);
+        });
+        rowprog::lookup_coeff_2(field, dl, dt, dm, rr, n, dh, dg, st);
+        z.close();
+        if (!host) SRS_HIP_CHECK(hipStreamSynchronize(st));
         SRS_HIP_CHECK(hipGetLastError());
         prof::collect();
         return SRS_OK;
@@ -2207,25 +2197,20 @@ int srs_batch_invert_assigned(int field, const srs_fe *numerators, const srs_fe 
     if (rc) return rc;
     return guarded([&]() -> int {
         hipStream_t st = (hipStream_t)stream;
-        if (space == SRS_SPACE_DEVICE) {
-            rowprog::assigned_invert(field, reinterpret_cast<const fe_t *>(numerators), reinterpret_cast<const fe_t *>(denominators),
-                                     has_denominator, n, reinterpret_cast<fe_t *>(out), st);
-            SRS_HIP_CHECK(hipStreamSynchronize(st));
-        } else {
-            g_scratch.reserve(3 * Arena::pad(n * sizeof(fe_t)) + Arena::pad(n) + 256);
-            g_scratch.reset();
-            fe_t *a = g_scratch.take<fe_t>(n), *b = g_scratch.take<fe_t>(n), *o = g_scratch.take<fe_t>(n);
-            uint8_t *h = nullptr;
-            SRS_HIP_CHECK(hipMemcpyAsync(a, numerators, n * sizeof(fe_t), hipMemcpyHostToDevice, st));
-            SRS_HIP_CHECK(hipMemcpyAsync(b, denominators, n * sizeof(fe_t), hipMemcpyHostToDevice, st));
-            if (has_denominator) {
-                h = g_scratch.take<uint8_t>(n);
-                SRS_HIP_CHECK(hipMemcpyAsync(h, has_denominator, n, hipMemcpyHostToDevice, st));
-            }
-            rowprog::assigned_invert(field, a, b, h, n, o, st);
-            SRS_HIP_CHECK(hipMemcpyAsync(out, o, n * sizeof(fe_t), hipMemcpyDeviceToHost, st));
-            SRS_HIP_CHECK(hipStreamSynchronize(st));
-        }
+        const bool host = space != SRS_SPACE_DEVICE;
+        Staging z(g_scratch, st, host);
+        const fe_t *num = nullptr, *den = nullptr;
+        const uint8_t *has = nullptr;
+        fe_t *o = nullptr;
+        z.place([&] {
+            num = z.in(reinterpret_cast<const fe_t *>(numerators), n);
+            den = z.in(reinterpret_cast<const fe_t *>(denominators), n);
+            if (has_denominator) has = z.in(has_denominator, n);
+            o = z.out(reinterpret_cast<fe_t *>(out), n);
+        });
+        rowprog::assigned_invert(field, num, den, has, n, o, st);
+        z.close();
+        if (!host) SRS_HIP_CHECK(hipStreamSynchronize(st));
         SRS_HIP_CHECK(hipGetLastError());
         return SRS_OK;
     });
@@ -2239,15 +2224,10 @@ int srs_is_sat_log_derivative(srs_structure *S, const srs_fe *W, int space, void
         hipStream_t st = (hipStream_t)stream;
         rowprog::Structure *s = S->s;
         const size_t wlen = rowprog::num_witness_columns(s) * rowprog::rows(s);
-        const fe_t *dW = reinterpret_cast<const fe_t *>(W);
-        if (space != SRS_SPACE_DEVICE && rowprog::num_lookups(s)) {
-            S->io.reserve(Arena::pad((wlen + 1) * sizeof(fe_t)) + 1024);
-            S->io.reset();
-            fe_t *a = S->io.take<fe_t>(wlen + 1);
-            SRS_HIP_CHECK(hipMemcpyAsync(a, W, wlen * sizeof(fe_t), hipMemcpyHostToDevice, st));
-            dW = a;
-        }
-        *mismatch_count = rowprog::log_derivative_mismatches(s, dW, st);
+        Staging z(S->io, st, space != SRS_SPACE_DEVICE && rowprog::num_lookups(s));      // without lookups W is not read: not staged
+        const fe_t *dW = nullptr;
+        z.place([&] { dW = z.in(reinterpret_cast<const fe_t *>(W), wlen); });
+        *mismatch_count = rowprog::log_derivative_mismatches(s, dW, st);      // ends synchronised
         return SRS_OK;
     });
 }
@@ -2262,19 +2242,18 @@ int srs_fold_witness(int field, srs_fe *out, const srs_fe *w1, const srs_fe *w2,
         hipStream_t st = (hipStream_t)stream;
         fe_t rr;
         std::memcpy(&rr, r, 32);
-        if (space == SRS_SPACE_DEVICE) {
-            // device-resident operands: stream-ordered (the result is ready in `stream` order, like any library kernel)
-            rowprog::fold_w(field, reinterpret_cast<fe_t *>(out), reinterpret_cast<const fe_t *>(w1), reinterpret_cast<const fe_t *>(w2), rr, n, st);
-        } else {
-            g_scratch.reserve(2 * Arena::pad(n * sizeof(fe_t)) + 256);
-            g_scratch.reset();
-            fe_t *a = g_scratch.take<fe_t>(n), *b = g_scratch.take<fe_t>(n);
-            SRS_HIP_CHECK(hipMemcpyAsync(a, w1, n * sizeof(fe_t), hipMemcpyHostToDevice, st));
-            SRS_HIP_CHECK(hipMemcpyAsync(b, w2, n * sizeof(fe_t), hipMemcpyHostToDevice, st));
-            rowprog::fold_w(field, a, a, b, rr, n, st);
-            SRS_HIP_CHECK(hipMemcpyAsync(out, a, n * sizeof(fe_t), hipMemcpyDeviceToHost, st));
-            SRS_HIP_CHECK(hipStreamSynchronize(st));
-        }
+        // device-resident operands: stream-ordered (the result is ready in `stream` order, like any library kernel); host operands: folded
+        // into the staged copy of w1
+        Staging z(g_scratch, st, space != SRS_SPACE_DEVICE);
+        const fe_t *a = nullptr, *b = nullptr;
+        fe_t *o = nullptr;
+        z.place([&] {
+            a = z.in(reinterpret_cast<const fe_t *>(w1), n);
+            b = z.in(reinterpret_cast<const fe_t *>(w2), n);
+            o = z.out_into(reinterpret_cast<fe_t *>(out), a, n);
+        });
+        rowprog::fold_w(field, o, a, b, rr, n, st);
+        z.close();
         SRS_HIP_CHECK(hipGetLastError());
         return SRS_OK;
     });
@@ -2291,26 +2270,18 @@ int srs_fold_error(int field, srs_fe *out, const srs_fe *e, const srs_fe *const 
         fe_t rr;
         std::memcpy(&rr, r, 32);
         std::string err;
-        if (space == SRS_SPACE_DEVICE) {
-            int erc = rowprog::fold_e(field, reinterpret_cast<fe_t *>(out), reinterpret_cast<const fe_t *>(e),
-                                      reinterpret_cast<const fe_t *const *>(T), n_terms, rr, n, st, err);
-            if (erc) return fail(erc, "srs_fold_error: " + err);   // stream-ordered, see srs_fold_witness
-        } else {
-            g_scratch.reserve((n_terms + 1) * Arena::pad(n * sizeof(fe_t)) + 256);
-            g_scratch.reset();
-            fe_t *buf = g_scratch.take<fe_t>(n);
-            SRS_HIP_CHECK(hipMemcpyAsync(buf, e, n * sizeof(fe_t), hipMemcpyHostToDevice, st));
-            std::vector<const fe_t *> tp(n_terms);
-            for (size_t k = 0; k < n_terms; ++k) {
-                fe_t *t = g_scratch.take<fe_t>(n);
-                SRS_HIP_CHECK(hipMemcpyAsync(t, T[k], n * sizeof(fe_t), hipMemcpyHostToDevice, st));
-                tp[k] = t;
-            }
-            int erc = rowprog::fold_e(field, buf, buf, tp.data(), n_terms, rr, n, st, err);
-            if (erc) return fail(erc, "srs_fold_error: " + err);
-            SRS_HIP_CHECK(hipMemcpyAsync(out, buf, n * sizeof(fe_t), hipMemcpyDeviceToHost, st));
-            SRS_HIP_CHECK(hipStreamSynchronize(st));
-        }
+        Staging z(g_scratch, st, space != SRS_SPACE_DEVICE);       // stream-ordered / folded into the staged copy of e, see srs_fold_witness
+        const fe_t *de = nullptr;
+        fe_t *o = nullptr;
+        std::vector<const fe_t *> tp(n_terms);
+        z.place([&] {
+            de = z.in(reinterpret_cast<const fe_t *>(e), n);
+            for (size_t k = 0; k < n_terms; ++k) tp[k] = z.in(reinterpret_cast<const fe_t *>(T[k]), n);
+            o = z.out_into(reinterpret_cast<fe_t *>(out), de, n);
+        });
+        int erc = rowprog::fold_e(field, o, de, tp.data(), n_terms, rr, n, st, err);
+        if (erc) return fail(erc, "srs_fold_error: " + err);
+        z.close();
         SRS_HIP_CHECK(hipGetLastError());
         return SRS_OK;
     });
@@ -2342,17 +2313,10 @@ static int pg_impl(srs_structure *S, int mode, const srs_fe *weights, size_t n_w
         rowprog::Structure *s = S->s;
         const size_t wlen = rowprog::num_witness_columns(s) * rowprog::rows(s);
         std::vector<const fe_t *> dW(J);
-        if (space == SRS_SPACE_DEVICE) {
-            for (size_t j = 0; j < J; ++j) dW[j] = reinterpret_cast<const fe_t *>(W[j]);
-        } else {
-            S->io.reserve(J * Arena::pad((wlen + 1) * sizeof(fe_t)) + 1024);
-            S->io.reset();
-            for (size_t j = 0; j < J; ++j) {
-                fe_t *d = S->io.take<fe_t>(wlen + 1);
-                SRS_HIP_CHECK(hipMemcpyAsync(d, W[j], wlen * sizeof(fe_t), hipMemcpyHostToDevice, st));
-                dW[j] = d;
-            }
-        }
+        Staging z(S->io, st, space != SRS_SPACE_DEVICE);
+        z.place([&] {
+            for (size_t j = 0; j < J; ++j) dW[j] = z.in(reinterpret_cast<const fe_t *>(W[j]), wlen);
+        });
         std::vector<const fe_t *> ch(J);
         for (size_t j = 0; j < J; ++j) ch[j] = n_challenges ? reinterpret_cast<const fe_t *>(challenges[j]) : nullptr;
         std::string err;
@@ -2401,18 +2365,30 @@ int srs_pg_compute_K_from_G(const srs_fe *poly_G, size_t n_G, const srs_fe *poly
     });
 }
 
-int srs_pg_beta_stroke(const srs_fe *betas, size_t n, const srs_fe *alpha, const srs_fe *delta, srs_fe *out) {
-    if ((n && (!betas || !out)) || !alpha || !delta) return fail(SRS_ERR_INVALID, "srs_pg_beta_stroke: bad argument");
-    fe_t a, d;
-    std::memcpy(&a, alpha, 32);
+// BetaStrokeIter: out[i] = beta[i] + alpha * delta^(2^i)   (poly/mod.rs:449-462)
+static void pg_beta_stroke(const srs_fe *betas, size_t n, const fe_t &alpha, const srs_fe *delta, srs_fe *out) {
+    fe_t d;
     std::memcpy(&d, delta, 32);
-    for (size_t i = 0; i < n; ++i) {                   // BetaStrokeIter: next = beta[i] + alpha * delta^(2^i)   (poly/mod.rs:449-462)
+    for (size_t i = 0; i < n; ++i) {
         fe_t b;
         std::memcpy(&b, &betas[i], 32);
-        b = Fr::add(b, Fr::mul(a, d));
+        b = Fr::add(b, Fr::mul(alpha, d));
         std::memcpy(&out[i], &b, 32);
         d = Fr::sqr(d);
     }
+}
+// e = F(alpha) L_0(gamma) + Z(gamma) K(gamma)  (calculate_e, protogalaxy/mod.rs:748-764; Z: eval_vanish_polynomial, lagrange.rs:83-85)
+static fe_t pg_calculate_e(const fe_t &f_alpha, const fe_t &l0, const srs_fe *poly_K, size_t n_K, const fe_t &gamma, uint32_t log_n) {
+    const fe_t z = Fr::sub(Fr::pow_u64(gamma, (uint64_t)1 << log_n), Fr::one());
+    const fe_t kg = rowprog::poly_eval(reinterpret_cast<const fe_t *>(poly_K), n_K, gamma);
+    return Fr::add(Fr::mul(f_alpha, l0), Fr::mul(z, kg));
+}
+
+int srs_pg_beta_stroke(const srs_fe *betas, size_t n, const srs_fe *alpha, const srs_fe *delta, srs_fe *out) {
+    if ((n && (!betas || !out)) || !alpha || !delta) return fail(SRS_ERR_INVALID, "srs_pg_beta_stroke: bad argument");
+    fe_t a;
+    std::memcpy(&a, alpha, 32);
+    pg_beta_stroke(betas, n, a, delta, out);
     return SRS_OK;
 }
 
@@ -2448,11 +2424,8 @@ int srs_pg_calculate_e(const srs_fe *poly_F, size_t n_F, const srs_fe *poly_K, s
     fe_t g, a;
     std::memcpy(&g, gamma, 32);
     std::memcpy(&a, alpha, 32);
-    fe_t l0 = rowprog::lagrange_eval(g, log_n)[0];
-    fe_t fa = rowprog::poly_eval(reinterpret_cast<const fe_t *>(poly_F), n_F, a);
-    fe_t z = Fr::sub(Fr::pow_u64(g, (uint64_t)1 << log_n), Fr::one());      // eval_vanish_polynomial, lagrange.rs:83-85
-    fe_t kg = rowprog::poly_eval(reinterpret_cast<const fe_t *>(poly_K), n_K, g);
-    fe_t r = Fr::add(Fr::mul(fa, l0), Fr::mul(z, kg));
+    const fe_t fa = rowprog::poly_eval(reinterpret_cast<const fe_t *>(poly_F), n_F, a);
+    const fe_t r = pg_calculate_e(fa, rowprog::lagrange_eval(g, log_n)[0], poly_K, n_K, g, log_n);
     std::memcpy(out, &r, 32);
     return SRS_OK;
 }
@@ -2524,16 +2497,7 @@ int srs_pg_prove(srs_structure *S, srs_poseidon *ro, const srs_fe *betas, size_t
         }
         // betas_stroke (BetaStrokeIter :449-462), F(alpha)
         std::vector<fe_t> bs(z.betas_count);
-        {
-            fe_t d;
-            std::memcpy(&d, delta, 32);
-            for (size_t i = 0; i < z.betas_count; ++i) {
-                fe_t b;
-                std::memcpy(&b, &betas[i], 32);
-                bs[i] = Fr::add(b, Fr::mul(alpha, d));
-                d = Fr::sqr(d);
-            }
-        }
+        pg_beta_stroke(betas, z.betas_count, alpha, delta, reinterpret_cast<srs_fe *>(bs.data()));
         const fe_t f_alpha = rowprog::poly_eval(reinterpret_cast<const fe_t *>(poly_F), z.points_F, alpha);
         ht.mark("alpha,betas'");
         // poly_K = compute_K(F(alpha), betas_stroke, accumulator, incoming)                               :437-443
@@ -2571,11 +2535,9 @@ int srs_pg_prove(srs_structure *S, srs_poseidon *ro, const srs_fe *betas, size_t
             if (!poseidon::squeeze(*ro->h, 255, SRS_FIELD_FR, gamma, err)) return fail(SRS_ERR_INVALID, "srs_pg_prove (gamma): " + err);
         }
         ht.mark("gamma");
-        // L_j(gamma), e = F(alpha) L_0(gamma) + Z(gamma) K(gamma)  (calculate_e :748-764), fold_witness :176-210
+        // L_j(gamma), e (calculate_e :748-764), fold_witness :176-210
         const std::vector<fe_t> L = rowprog::lagrange_eval(gamma, (uint32_t)z.lagrange_domain);
-        const fe_t zg = Fr::sub(Fr::pow_u64(gamma, (uint64_t)1 << z.lagrange_domain), Fr::one());
-        const fe_t kg = rowprog::poly_eval(reinterpret_cast<const fe_t *>(poly_K), n_K, gamma);
-        const fe_t ev = Fr::add(Fr::mul(f_alpha, L[0]), Fr::mul(zg, kg));
+        const fe_t ev = pg_calculate_e(f_alpha, L[0], poly_K, n_K, gamma, (uint32_t)z.lagrange_domain);
         if (W_folded) {      // NULL: the caller folds later (srs_fold_lincomb with `lagrange`), e.g. under the next witness upload
             erc = rowprog::lincomb(SRS_FIELD_FR, reinterpret_cast<fe_t *>(W_folded), dW.data(), L.data(), n_instances, wlen, st, err);
             if (erc) return fail(erc, "srs_pg_prove (fold_witness): " + err);
@@ -2622,9 +2584,7 @@ static int sangria_prove_impl(srs_structure *S, srs_ck *ck, srs_poseidon *ro, co
         if (rowprog::num_challenges(S->s) != 0)
             return fail(SRS_ERR_INVALID, "srs_sangria_prove_incoming: the structure has challenges (they depend on the trace's commitment); "
                                          "commit the trace first (srs_commit_upload), then srs_sangria_prove");
-        if (wlen > ck->key.global_len || rows > ck->key.global_len)
-            return fail(SRS_ERR_TOO_LONG_INPUT, "Can't commit too long input: input len: " + std::to_string(std::max(wlen, rows)) +
-                                                    ", but limit is " + std::to_string(ck->key.global_len));
+        if (wlen > ck->key.global_len || rows > ck->key.global_len) return too_long_input(std::max(wlen, rows), ck);
         rc = ensure_device();
         if (rc) return rc;
         std::vector<affine_t> cm(d + 1);
@@ -2712,26 +2672,17 @@ int srs_fold_lincomb(int field, srs_fe *out, const srs_fe *const *W, const srs_f
     return guarded([&]() -> int {
         hipStream_t st = (hipStream_t)stream;
         std::string err;
-        if (space == SRS_SPACE_DEVICE) {
-            int erc = rowprog::lincomb(field, reinterpret_cast<fe_t *>(out), reinterpret_cast<const fe_t *const *>(W),
-                                       reinterpret_cast<const fe_t *>(coefs), J, n, st, err);
-            if (erc) return fail(erc, "srs_fold_lincomb: " + err);   // stream-ordered, see srs_fold_witness
-        } else {
-            fe_t *buf = nullptr;
-            SRS_HIP_CHECK(hipMalloc((void **)&buf, J * n * sizeof(fe_t)));
-            try {
-                std::vector<const fe_t *> wp(J);
-                for (size_t j = 0; j < J; ++j) {
-                    SRS_HIP_CHECK(hipMemcpyAsync(buf + j * n, W[j], n * sizeof(fe_t), hipMemcpyHostToDevice, st));
-                    wp[j] = buf + j * n;
-                }
-                int erc = rowprog::lincomb(field, buf, wp.data(), reinterpret_cast<const fe_t *>(coefs), J, n, st, err);
-                if (erc) { (void)hipFree(buf); return fail(erc, "srs_fold_lincomb: " + err); }
-                SRS_HIP_CHECK(hipMemcpyAsync(out, buf, n * sizeof(fe_t), hipMemcpyDeviceToHost, st));
-                SRS_HIP_CHECK(hipStreamSynchronize(st));
-            } catch (...) { (void)hipFree(buf); throw; }
-            (void)hipFree(buf);
-        }
+        ScopedArena transient;
+        Staging z(transient, st, space != SRS_SPACE_DEVICE);       // stream-ordered / folded into the staged copy of W[0], see srs_fold_witness
+        std::vector<const fe_t *> wp(J);
+        fe_t *o = nullptr;
+        z.place([&] {
+            for (size_t j = 0; j < J; ++j) wp[j] = z.in(reinterpret_cast<const fe_t *>(W[j]), n);
+            o = z.out_into(reinterpret_cast<fe_t *>(out), wp[0], n);
+        });
+        int erc = rowprog::lincomb(field, o, wp.data(), reinterpret_cast<const fe_t *>(coefs), J, n, st, err);
+        if (erc) return fail(erc, "srs_fold_lincomb: " + err);
+        z.close();
         SRS_HIP_CHECK(hipGetLastError());
         return SRS_OK;
     });
