@@ -1190,6 +1190,216 @@ static void launch_pg_leaves(const PgArgs &A, uint32_t tiles, uint32_t gates, ui
 }
 
 // ---------------------------------------------------------------------------------------------
+// What the routes of the sums share: the evaluation points, the gates' uniform tables, the kernels' argument block,
+// the leaf launches, the integer-node interpolation and the end of a call.  The routes themselves: pg_row0_values (closed form),
+// pg_F_tree, pg_leaf_sums; pg_sum dispatches.
+// ---------------------------------------------------------------------------------------------
+constexpr uint32_t PG_LPT = 8;      // leaves per thread once a gate has >= 1024 rows; the sweep kernels read their own table at slot PG_LPT
+
+// what ends a call: the staging lives in the structure's arena until the stream has drained
+static void finish(hipStream_t st) {
+    SRS_HIP_CHECK(hipStreamSynchronize(st));
+    SRS_HIP_CHECK(hipGetLastError());
+    prof::collect();
+}
+
+static std::vector<fe_t> pg_deltas(const fe_t &delta, uint32_t levels) {      // delta^(2^b)  (:97-99)
+    std::vector<fe_t> out(levels);
+    fe_t d = delta;
+    for (uint32_t b = 0; b < levels; ++b) { out[b] = d; d = Fr::sqr(d); }
+    return out;
+}
+
+struct PgPoints {
+    std::vector<fe_t> pts;                       // X_p: the integers pt0 .. pt0 + P - 1, or the P roots of unity (iter_cyclic_subgroup)
+    std::vector<fe_t> wcoef;                     // fold: [P][J] = L_j(X_p)   (FoldedWitness::new, folded_witness.rs:20-47)
+    std::vector<std::vector<fe_t>> ch_pt;        // the challenges per leaf point: fold ? the J traces' folded with L_j(X_p) : trace 0's
+};
+// fold = false (compute_F, evaluate_e): one leaf point on W_dev[0]; the P points are F's.  fold = true (compute_G): P leaf points
+static PgPoints pg_points(bool g_int, uint32_t pt0, uint32_t P, bool fold, size_t J, uint32_t lagrange_domain, const fe_t *const *challenges_host,
+                          size_t n_ch) {
+    PgPoints o;
+    const fe_t w = g_int || P == 1 ? Fr::one() : ntt::omega(ilog2(P), false);
+    fe_t x = Fr::one();
+    for (uint32_t p = 0; p < P; ++p) { o.pts.push_back(g_int ? Fr::from_u64(pt0 + p) : x); x = Fr::mul(x, w); }
+    o.ch_pt.assign(fold ? P : 1, std::vector<fe_t>(n_ch ? n_ch : 1, Fr::zero()));
+    if (!fold) {
+        for (size_t c = 0; c < n_ch; ++c) o.ch_pt[0][c] = challenges_host[0][c];
+        return o;
+    }
+    o.wcoef.resize((size_t)P * J);
+    // integer-point G folds the witnesses by halvings in the kernel: L_j(X_p) is only needed to fold challenges
+    for (uint32_t p = 0; p < P && (!g_int || n_ch); ++p) {
+        std::vector<fe_t> L = lagrange_eval(o.pts[p], lagrange_domain);
+        for (size_t j = 0; j < J; ++j) {
+            o.wcoef[(size_t)p * J + j] = L[j];
+            for (size_t c = 0; c < n_ch; ++c)                 // fold_plonk_challenges :142-180
+                o.ch_pt[p][c] = Fr::add(o.ch_pt[p][c], Fr::mul(challenges_host[j][c], L[j]));
+        }
+    }
+    return o;
+}
+
+// The sweep form of a gate's table (k_pg_leaves_sweep): PG_LPT + 1 tables.  Table 0 is the plain one; table l in [first, PG_LPT] holds the
+// term coefficients (sw_coef) times w[l], one table per leaf slot of a thread -- or, not `weighted`, as they are: what row 0 (hoist_mode 1)
+// reads at table PG_LPT.  The tables below `first` stay zero.
+struct PgSlotWeights { uint32_t first; bool weighted; fe_t w[PG_LPT + 1]; };
+// the leaf pass: w_l = prod_{b in bits(l)} c[b], c = the weights of the three levels a thread reduces in registers; table PG_LPT: the SUM of
+// the w_l, l = 0 .. PG_LPT - 1 (reference_compat: the leaves of a thread share one evaluation at row 0)
+static PgSlotWeights pg_slot_weights_leaves(const fe_t *c) {
+    PgSlotWeights s;
+    s.first = 1;
+    s.weighted = true;
+    fe_t wsum = Fr::one();
+    for (uint32_t l = 1; l < PG_LPT; ++l) {
+        fe_t wl = Fr::one();
+        for (uint32_t b = 0; b < 3; ++b)
+            if ((l >> b) & 1u) wl = Fr::mul(wl, c[b]);
+        s.w[l] = wl;
+        wsum = Fr::add(wsum, wl);
+    }
+    s.w[0] = Fr::one();
+    s.w[PG_LPT] = wsum;
+    return s;
+}
+
+struct PgGateTable {
+    std::vector<GateProg> gp;
+    std::vector<fe_t> utab;                      // per gate: [sw ? PG_LPT + 1 : 1][leaf points][n_uniform]
+    uint32_t max_slots = 1;
+};
+// gp[], utab and max_slots of the structure's gates for the challenges ch_pt[leaf point]; sw: the sweep form, or nullptr
+static int pg_gate_table(Structure *S, const std::vector<std::vector<fe_t>> &ch_pt, size_t n_ch, const PgSlotWeights *sw, PgGateTable &t, std::string &err) {
+    FieldOps f{0};
+    const uint32_t n_gates = (uint32_t)S->gate_progs.size(), leaf_pts = (uint32_t)ch_pt.size();
+    t.gp.resize(n_gates);
+    for (uint32_t g = 0; g < n_gates; ++g) {
+        Program &p = S->gate_progs[g];
+        GateProg &gp = t.gp[g];
+        t.max_slots = std::max(t.max_slots, p.nslots);
+        const size_t nu = p.uops.size() ? p.uops.size() : 1;
+        gp.prog = p.d_insns;
+        gp.n_insn = (uint32_t)p.insns.size();
+        gp.result = p.result;
+        gp.n_uniform = (uint32_t)nu;
+        gp.utab_off = (uint32_t)t.utab.size();
+        t.utab.resize(t.utab.size() + nu * leaf_pts * (sw ? PG_LPT + 1 : 1u));
+        fe_t *tab = t.utab.data() + gp.utab_off;
+        for (uint32_t lp = 0; lp < leaf_pts; ++lp)
+            if (!eval_uniform(p, f, ch_pt[lp].data(), n_ch, 0, false, 0, tab + (size_t)lp * nu, err)) return 7;
+        for (uint32_t l = sw ? sw->first : PG_LPT + 1; l <= PG_LPT; ++l) {
+            fe_t *dst = tab + (size_t)l * leaf_pts * nu;
+            std::memcpy(dst, tab, (size_t)leaf_pts * nu * sizeof(fe_t));
+            for (uint32_t lp = 0; lp < leaf_pts && sw->weighted; ++lp)
+                for (int ci : p.sw_coef) dst[(size_t)lp * nu + ci] = Fr::mul(dst[(size_t)lp * nu + ci], sw->w[l]);
+        }
+    }
+    if (t.max_slots > 32) { err = "row program needs more than 32 live registers"; return 4; }
+    return 0;
+}
+
+struct PgCall {                                  // what the callers of pg_args differ in
+    size_t n_w = 1;                              // witness pointers handed over
+    uint32_t J = 1;                              // witnesses folded at every leaf point (compute_G), else 1
+    const fe_t *wcoef = nullptr;                 // device [P][J] = L_j(X_p); nullptr: no fold, or the fold by halvings (`half`)
+    uint32_t half = 0, pt0 = 0;                  // integer-point G: the nodes pt0, pt0 + 1, ..
+    int compat = 1;
+    uint32_t leaf_pts = 1, P = 1, wpts = 1, tile_log = 0;
+    const fe_t *weights = nullptr;
+    fe_t *partial = nullptr, *hoist = nullptr;
+    bool sharded = false;
+};
+// The kernels' argument block.  A row-sharded structure (set_shard), one rule, three callers:
+//   pg_row0_values: unsharded -- every rank holds row 0, and pg_sum answers for the ranks >= 1 without a launch.
+//   pg_F_tree, and pg_leaf_sums at k >= 10 (tile_log == STRIPE_LOG, a tile IS a stripe): the structure's rank and world -- this rank's tiles.
+//   pg_leaf_sums with smaller tiles: rank 0 evaluates everything, no tile belongs to the other ranks.
+// The rows themselves (ctx) are never sharded here: a tile reads all of its rows.
+static PgArgs pg_args(const Structure *S, const fe_t *const *W_dev, const GateProg *d_gp, const fe_t *d_utab, const PgCall &c) {
+    PgArgs a;
+    a.gates = d_gp;
+    a.n_gates = (uint32_t)S->gate_progs.size();
+    a.log_rows = S->k;
+    a.ctx.rows = (uint32_t)S->rows;
+    a.ctx.sel = S->d_sel_ptrs;
+    a.ctx.fix = S->d_fix_ptrs;
+    for (uint32_t j = 0; j < JMAX; ++j) a.ctx.W[j] = j < c.n_w ? W_dev[j] : nullptr;
+    a.ctx.J = c.J;
+    a.ctx.wcoef = c.wcoef;
+    a.ctx.half = c.half;
+    a.ctx.pt0 = c.pt0;
+    a.ctx.shard_rank = 0;
+    a.ctx.shard_world = 1;
+    a.ctx.local_rows = a.ctx.rows;
+    a.compat = c.compat;
+    a.leaf_pts = c.leaf_pts;
+    a.P = c.P;
+    a.utab = d_utab;
+    a.weights = c.weights;
+    a.wpts = c.wpts;
+    a.tile_log = c.tile_log;
+    a.partial = c.partial;
+    a.shard_rank = 0;
+    a.shard_world = 1;
+    if (c.sharded && c.tile_log == STRIPE_LOG) { a.shard_rank = S->shard_rank; a.shard_world = S->shard_world; }
+    else if (c.sharded && S->shard_world > 1 && S->shard_rank != 0) { a.shard_rank = 0xFFFFFFFFu; a.shard_world = 2; }     // no tile is mine
+    a.hoist = c.hoist;
+    a.hoist_mode = 0;
+    return a;
+}
+
+// one leaf launch: the ahead-of-time gate set (8 leaves per thread only; sweep: its sweep form), else the interpreter by live registers
+static void launch_leaves(const Structure *S, const PgArgs &a, uint32_t tiles, uint32_t threads, uint32_t lpt, uint32_t max_slots, bool sweep,
+                          hipStream_t st) {
+    if (S->pg_spec_id >= 0 && lpt == PG_LPT) launch_pg_spec(S->pg_spec_id, a, tiles, a.n_gates, threads, st, sweep);
+    else if (max_slots <= 8) launch_pg_leaves<8>(a, tiles, a.n_gates, threads, lpt, st);
+    else if (max_slots <= 12) launch_pg_leaves<12>(a, tiles, a.n_gates, threads, lpt, st);
+    else if (max_slots <= 16) launch_pg_leaves<16>(a, tiles, a.n_gates, threads, lpt, st);
+    else launch_pg_leaves<32>(a, tiles, a.n_gates, threads, lpt, st);
+}
+
+static void launch_F_leaves(const Structure *S, const PgArgs &a, const PgFLevels &lv, uint32_t tiles, uint32_t threads, uint32_t max_slots, fe_t *out,
+                            uint32_t n0, hipStream_t st) {
+    if (S->pg_spec_id == 0) SRS_LAUNCH((k_pg_F_leaves<Fr, 2, 0>), (tiles, a.n_gates), (threads), 0, st, a, lv, out, n0);
+    else if (max_slots <= 8) SRS_LAUNCH((k_pg_F_leaves<Fr, 8, -1>), (tiles, a.n_gates), (threads), 0, st, a, lv, out, n0);
+    else if (max_slots <= 16) SRS_LAUNCH((k_pg_F_leaves<Fr, 16, -1>), (tiles, a.n_gates), (threads), 0, st, a, lv, out, n0);
+    else SRS_LAUNCH((k_pg_F_leaves<Fr, 32, -1>), (tiles, a.n_gates), (threads), 0, st, a, lv, out, n0);
+}
+
+// hoist (the reference's leaf rows): the gates at row 0 once, `row0_groups` workgroups per gate (hoist_mode 1), then the leaf pass reads
+// them (hoist_mode 2).  Otherwise the leaf pass alone.
+template <class Launch>
+static void launch_hoisted(PgArgs &a, bool hoist, uint32_t row0_groups, uint32_t tiles, Launch &&leaves) {
+    if (hoist) {
+        a.hoist_mode = 1;
+        leaves(row0_groups);
+        a.hoist_mode = 2;
+    }
+    leaves(tiles);
+}
+
+// the inverse Vandermonde matrix [d + 1][d + 1] of the integer nodes first .. first + d, first = 0 | 1: coefficient k = sum_j M[k][j] value_j
+static std::vector<fe_t> pg_node_matrix(const Structure *S, uint32_t d, uint32_t first) {
+    FieldOps f{0};
+    if (first) return !S->vinv_g1.empty() ? S->vinv_g1 : inverse_vandermonde_at(f, d, 1);
+    const std::vector<fe_t> rows = !S->vinv_g.empty() ? S->vinv_g : (d ? inverse_vandermonde_rows(f, d) : std::vector<fe_t>());      // rows k = 1 .. d
+    std::vector<fe_t> full((size_t)(d + 1) * (d + 1), Fr::zero());
+    full[0] = Fr::one();                                       // coefficient 0 = the value at node 0
+    std::copy(rows.begin(), rows.end(), full.begin() + (d + 1));
+    return full;
+}
+
+// out[0 .. n_out): the coefficients of the polynomial of degree <= d_G with `values` at the nodes first_node .. first_node + d_G, then zeros
+static void pg_interpolate(const Structure *S, const fe_t *values, uint32_t first_node, fe_t *out, size_t n_out) {
+    const uint32_t n = (uint32_t)S->max_gate_degree + 1;
+    const std::vector<fe_t> M = pg_node_matrix(S, n - 1, first_node);
+    for (size_t k = 0; k < n_out; ++k) {
+        fe_t acc = Fr::zero();
+        for (uint32_t j = 0; j < n && k < n; ++j) acc = Fr::add(acc, Fr::mul(M[k * n + j], values[j]));
+        out[k] = acc;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // The reference's leaf rows in closed form (reference_compat).  Every leaf of gate g is that gate AT ROW 0
 // (src/plonk/mod.rs:714), one value c_g per (gate, point), and the weights are products over the index bits, pow_i(w) =
 // prod_b w_b^bit_b(i), so the sum over gate g's aligned block of 2^k leaves factors:
@@ -1212,11 +1422,7 @@ fe_t pg_closed_sum(const fe_t *c, size_t stride, uint32_t n_gates, uint32_t k, c
 
 // compute_F: the same sum with the weights beta_b + X delta^(2^b), a product of linear polynomials: out[0 .. n_out), degree <= levels
 void pg_closed_F(const fe_t *c, uint32_t n_gates, uint32_t k, const fe_t *betas, const fe_t &delta, uint32_t levels, fe_t *out, size_t n_out) {
-    std::vector<fe_t> deltas(levels);
-    {
-        fe_t d = delta;                                        // deltas: delta^(2^b)  (:97-99)
-        for (uint32_t b = 0; b < levels; ++b) { deltas[b] = d; d = Fr::sqr(d); }
-    }
+    const std::vector<fe_t> deltas = pg_deltas(delta, levels);
     // p(X) *= (a + X d), deg = current degree
     auto mul_linear = [](std::vector<fe_t> &p, uint32_t &deg, const fe_t &a, const fe_t &d) {
         p[deg + 1] = Fr::mul(p[deg], d);
@@ -1246,19 +1452,8 @@ void pg_closed_G(const Structure *S, const PgRow0 &r0, const fe_t *betas_stroke,
     std::vector<fe_t> val(P);
     for (uint32_t p = 0; p < P; ++p) val[p] = pg_closed_sum(r0.vals.data() + p, P, n_gates, S->k, betas_stroke, levels);
     if (point_values) *point_values = val;
+    if (r0.g_int) { pg_interpolate(S, val.data(), 0, out, n_out); return; }
     for (size_t m = 0; m < n_out; ++m) out[m] = Fr::zero();
-    if (r0.g_int) {
-        const uint32_t dG = P - 1;
-        FieldOps f{0};
-        const std::vector<fe_t> vinv = !S->vinv_g.empty() ? S->vinv_g : (dG ? inverse_vandermonde_rows(f, dG) : std::vector<fe_t>());    // [dG][dG + 1], rows k = 1..dG
-        out[0] = val[0];                                                                            // G(0)
-        for (uint32_t k = 1; k <= dG && k < n_out; ++k) {
-            fe_t acc = Fr::zero();
-            for (uint32_t j = 0; j < P; ++j) acc = Fr::add(acc, Fr::mul(vinv[(size_t)(k - 1) * P + j], val[j]));
-            out[k] = acc;
-        }
-        return;
-    }
     const fe_t winv = ntt::omega(ilog2(P), true), inv_P = Fr::inv(Fr::from_u64(P));
     fe_t wk = Fr::one();                                       // winv^k
     for (uint32_t k = 0; k < P && k < n_out; ++k) {
@@ -1279,117 +1474,292 @@ int pg_row0_values(Structure *S, bool fold, const fe_t *const *W_dev, const fe_t
     if (J == 0 || J > JMAX) { err = "unsupported number of traces"; return 4; }
     PgSizes sz;
     if (!pg_sizes(S, fold ? J - 1 : 1, sz)) { err = "structure has no gates"; return 4; }
-    FieldOps f{0};
     const bool g_int = fold && J == 2 && tuning::get_or(tuning::PG_G_FFT, 0) == 0;
     const uint32_t P = !fold ? 1u : (g_int ? (uint32_t)S->max_gate_degree + 1 : (uint32_t)sz.points_G);
     const uint32_t n_gates = (uint32_t)S->gate_progs.size();
     out.P = P;
     out.g_int = g_int;
     out.one_at = g_int ? 1u : 0u;                              // integer nodes 0, 1, ..; roots of unity w^0 = 1, w, ..
-    std::vector<fe_t> wcoef;                                   // [P][J] = L_j(X_p)   (FoldedWitness::new, folded_witness.rs:20-47)
-    std::vector<std::vector<fe_t>> ch_pt(P, std::vector<fe_t>(n_ch ? n_ch : 1, Fr::zero()));
-    if (fold) {
-        wcoef.resize((size_t)P * J);
-        const fe_t w = g_int ? Fr::one() : ntt::omega(ilog2(P), false);
-        fe_t x = g_int ? Fr::zero() : Fr::one();
-        for (uint32_t p = 0; p < P; ++p) {
-            // integer-point G folds the witnesses by halvings in the kernel: L_j(X_p) is only needed to fold challenges
-            if (!g_int || n_ch) {
-                std::vector<fe_t> L = lagrange_eval(x, (uint32_t)sz.lagrange_domain);
-                for (size_t j = 0; j < J; ++j) {
-                    wcoef[(size_t)p * J + j] = L[j];
-                    for (size_t c = 0; c < n_ch; ++c)         // fold_plonk_challenges :142-180
-                        ch_pt[p][c] = Fr::add(ch_pt[p][c], Fr::mul(challenges_host[j][c], L[j]));
-                }
-            }
-            x = g_int ? Fr::add(x, Fr::one()) : Fr::mul(x, w);
-        }
-    } else {
-        for (size_t c = 0; c < n_ch; ++c) ch_pt[0][c] = challenges_host[0][c];
-    }
+    const PgPoints pp = pg_points(g_int, 0, P, fold, J, (uint32_t)sz.lagrange_domain, challenges_host, n_ch);
     // the specialised gate set in sweep form (k_pg_leaves_sweep<.., COMPAT>, hoist_mode 1) where the leaf route takes it, else the interpreter
     const bool sweep = S->pg_spec_id >= 0 && S->k >= 10 && (!fold || g_int) && P <= DMAX + 1;
-    const uint32_t lpt = 8;                                    // the sweep kernel reads its table at slot lpt
-    uint32_t max_slots = 1;
-    std::vector<GateProg> gp(n_gates);
-    std::vector<fe_t> utab;
-    for (uint32_t g = 0; g < n_gates; ++g) {
-        Program &p = S->gate_progs[g];
-        max_slots = std::max(max_slots, p.nslots);
-        const size_t nu = p.uops.size() ? p.uops.size() : 1;
-        gp[g].prog = p.d_insns;
-        gp[g].n_insn = (uint32_t)p.insns.size();
-        gp[g].result = p.result;
-        gp[g].n_uniform = (uint32_t)nu;
-        gp[g].utab_off = (uint32_t)utab.size();
-        utab.resize(utab.size() + nu * P * (sweep ? lpt + 1 : 1u));
-        fe_t *tab = utab.data() + gp[g].utab_off;
-        for (uint32_t lp = 0; lp < P; ++lp)
-            if (!eval_uniform(p, f, ch_pt[lp].data(), n_ch, 0, false, 0, tab + (size_t)lp * nu, err)) return 7;
-        if (sweep) std::memcpy(tab + (size_t)lpt * P * nu, tab, (size_t)P * nu * sizeof(fe_t));      // the term coefficients as they are: no weight
-    }
-    if (max_slots > 32) { err = "row program needs more than 32 live registers"; return 4; }
+    PgSlotWeights sw;
+    sw.first = PG_LPT;
+    sw.weighted = false;
+    PgGateTable t;
+    if (int rc = pg_gate_table(S, pp.ch_pt, n_ch, sweep ? &sw : nullptr, t, err)) return rc;
     Arena &A = S->arena;
-    A.reserve(Arena::pad((wcoef.size() + 1) * sizeof(fe_t)) + Arena::pad((utab.size() + 1) * sizeof(fe_t)) + Arena::pad(gp.size() * sizeof(GateProg)) +
+    A.reserve(Arena::pad((pp.wcoef.size() + 1) * sizeof(fe_t)) + Arena::pad((t.utab.size() + 1) * sizeof(fe_t)) + Arena::pad(t.gp.size() * sizeof(GateProg)) +
               Arena::pad(((size_t)n_gates * P + 1) * sizeof(fe_t)) + 4096);
     A.reset();
-    fe_t *d_coef = A.take<fe_t>(wcoef.size() + 1);
-    fe_t *d_utab = A.take<fe_t>(utab.size() + 1);
-    GateProg *d_gp = A.take<GateProg>(gp.size());
+    fe_t *d_coef = A.take<fe_t>(pp.wcoef.size() + 1);
+    fe_t *d_utab = A.take<fe_t>(t.utab.size() + 1);
+    GateProg *d_gp = A.take<GateProg>(t.gp.size());
     fe_t *d_vals = A.take<fe_t>((size_t)n_gates * P + 1);
-    if (fold && !g_int) SRS_HIP_CHECK(hipMemcpyAsync(d_coef, wcoef.data(), wcoef.size() * sizeof(fe_t), hipMemcpyHostToDevice, st));
-    SRS_HIP_CHECK(hipMemcpyAsync(d_utab, utab.data(), utab.size() * sizeof(fe_t), hipMemcpyHostToDevice, st));
-    SRS_HIP_CHECK(hipMemcpyAsync(d_gp, gp.data(), gp.size() * sizeof(GateProg), hipMemcpyHostToDevice, st));
-    PgArgs a;
-    a.gates = d_gp;
-    a.n_gates = n_gates;
-    a.log_rows = S->k;
-    a.ctx.rows = (uint32_t)S->rows;
-    a.ctx.sel = S->d_sel_ptrs;
-    a.ctx.fix = S->d_fix_ptrs;
-    for (uint32_t j = 0; j < JMAX; ++j) a.ctx.W[j] = j < J ? W_dev[j] : nullptr;
-    a.ctx.J = (uint32_t)(fold ? J : 1);
-    a.ctx.wcoef = (fold && !g_int) ? d_coef : nullptr;
-    a.ctx.half = g_int ? 1u : 0u;
-    a.ctx.shard_rank = 0;
-    a.ctx.shard_world = 1;
-    a.ctx.local_rows = a.ctx.rows;
-    a.ctx.pt0 = 0;
-    a.compat = 1;
-    a.leaf_pts = P;
-    a.P = P;
-    a.utab = d_utab;
-    a.weights = nullptr;
-    a.wpts = 1;
-    a.tile_log = S->k >= 10 ? 10u : std::min<uint32_t>(7, S->k);
-    a.partial = nullptr;
-    a.shard_rank = 0;
-    a.shard_world = 1;
-    a.hoist = d_vals;
+    if (fold && !g_int) SRS_HIP_CHECK(hipMemcpyAsync(d_coef, pp.wcoef.data(), pp.wcoef.size() * sizeof(fe_t), hipMemcpyHostToDevice, st));
+    SRS_HIP_CHECK(hipMemcpyAsync(d_utab, t.utab.data(), t.utab.size() * sizeof(fe_t), hipMemcpyHostToDevice, st));
+    SRS_HIP_CHECK(hipMemcpyAsync(d_gp, t.gp.data(), t.gp.size() * sizeof(GateProg), hipMemcpyHostToDevice, st));
+    PgCall c;
+    c.n_w = J;
+    c.J = (uint32_t)(fold ? J : 1);
+    c.wcoef = (fold && !g_int) ? d_coef : nullptr;
+    c.half = g_int ? 1u : 0u;
+    c.leaf_pts = c.P = P;
+    c.tile_log = S->k >= 10 ? 10u : std::min<uint32_t>(7, S->k);
+    c.hoist = d_vals;
+    PgArgs a = pg_args(S, W_dev, d_gp, d_utab, c);
     a.hoist_mode = 1;
-    const uint32_t threads = (1u << a.tile_log) / (S->k >= 10 ? 8u : 1u);
     {
         prof::Scope ps("pg_row0", st, (size_t)n_gates * P);
-        if (sweep) launch_pg_spec(S->pg_spec_id, a, P, n_gates, threads, st, true);
-        else if (max_slots <= 8) launch_pg_leaves<8>(a, P, n_gates, threads, 1, st);
-        else if (max_slots <= 12) launch_pg_leaves<12>(a, P, n_gates, threads, 1, st);
-        else if (max_slots <= 16) launch_pg_leaves<16>(a, P, n_gates, threads, 1, st);
-        else launch_pg_leaves<32>(a, P, n_gates, threads, 1, st);
+        launch_leaves(S, a, P, (1u << a.tile_log) / (S->k >= 10 ? PG_LPT : 1u), sweep ? PG_LPT : 1u, t.max_slots, sweep, st);
     }
     out.vals.resize((size_t)n_gates * P);
     SRS_HIP_CHECK(hipMemcpyAsync(out.vals.data(), d_vals, out.vals.size() * sizeof(fe_t), hipMemcpyDeviceToHost, st));
-    SRS_HIP_CHECK(hipStreamSynchronize(st));
-    SRS_HIP_CHECK(hipGetLastError());
-    prof::collect();
+    finish(st);
     return 0;
 }
 
 bool pg_closed_route(int compat) { return compat && tuning::get_or(tuning::PG_COMPAT_TREE, 0) == 0; }
 
+// the reference's leaf rows: the gates at row 0 from the device, the sums in closed form on the host.  A row-sharded structure has
+// nothing to shard here (every rank holds row 0): rank 0 returns the whole polynomial, the others the zero polynomial
+static int pg_closed(Structure *S, int mode, const fe_t *const *W_dev, const fe_t *const *challenges_host, size_t n_ch, size_t J, const fe_t *weights_in,
+                     const fe_t *delta, uint32_t levels, hipStream_t st, fe_t *out_host, uint32_t P_out, std::string &err) {
+    for (uint32_t m = 0; m < P_out; ++m) out_host[m] = Fr::zero();
+    if (S->shard_world > 1 && S->shard_rank != 0) return 0;
+    PgRow0 r0;
+    const int rc = pg_row0_values(S, mode == 1, W_dev, challenges_host, n_ch, J, st, r0, err);
+    if (rc) return rc;
+    const uint32_t n_gates = (uint32_t)S->gate_progs.size();
+    if (mode == 0) pg_closed_F(r0.vals.data(), n_gates, S->k, weights_in, *delta, levels, out_host, P_out);
+    else if (mode == 1) pg_closed_G(S, r0, weights_in, levels, out_host, P_out);
+    else out_host[0] = pg_closed_sum(r0.vals.data(), 1, n_gates, S->k, weights_in, levels);
+    return 0;
+}
+
+// compute_F with >= 1024 rows per gate: the polynomial tree (see k_pg_F_leaves).  The leaves carry F's coefficients of the three levels
+// a thread reduces; the levels above multiply node polynomials by beta_b + X delta^(2^b).  -> out_host[0 .. P_out)
+static int pg_F_tree(Structure *S, const fe_t *const *W_dev, const fe_t *const *challenges_host, size_t n_ch, const fe_t *betas, const fe_t &delta,
+                     int compat, const PgSizes &sz, hipStream_t st, fe_t *out_host, uint32_t P_out, std::string &err) {
+    const uint32_t levels = (uint32_t)sz.betas_count, n_gates = (uint32_t)S->gate_progs.size();
+    const uint32_t tile_log = 10, TL = tile_log - 3, T = (1u << tile_log) / PG_LPT, tiles_per_gate = (uint32_t)(S->rows >> tile_log);
+    const size_t n_tiles_valid = (size_t)n_gates * tiles_per_gate, n_tiles_padded = sz.count_with_padding >> tile_log;
+    const PgPoints pp = pg_points(false, 0, 1, false, 1, 0, challenges_host, n_ch);
+    PgGateTable t;
+    if (int rc = pg_gate_table(S, pp.ch_pt, n_ch, nullptr, t, err)) return rc;
+    const size_t n0 = n_tiles_padded * T;
+    Arena &A = S->arena;
+    A.reserve(2 * Arena::pad((4 * n0 + 64) * sizeof(fe_t)) + Arena::pad((t.utab.size() + 1) * sizeof(fe_t)) +
+              Arena::pad(t.gp.size() * sizeof(GateProg)) + Arena::pad((n_gates + 1) * sizeof(fe_t)) + 4096);
+    A.reset();
+    fe_t *d_utab = A.take<fe_t>(t.utab.size() + 1);
+    GateProg *d_gp = A.take<GateProg>(t.gp.size());
+    fe_t *cur = A.take<fe_t>(4 * n0 + 64), *nxt = A.take<fe_t>(4 * n0 + 64);
+    fe_t *d_hoist = A.take<fe_t>(n_gates + 1);
+    SRS_HIP_CHECK(hipMemcpyAsync(d_utab, t.utab.data(), t.utab.size() * sizeof(fe_t), hipMemcpyHostToDevice, st));
+    SRS_HIP_CHECK(hipMemcpyAsync(d_gp, t.gp.data(), t.gp.size() * sizeof(GateProg), hipMemcpyHostToDevice, st));
+    const std::vector<fe_t> deltas = pg_deltas(delta, levels);
+    PgCall c;
+    c.compat = compat;
+    c.tile_log = tile_log;
+    c.sharded = true;
+    c.hoist = d_hoist;
+    PgArgs a = pg_args(S, W_dev, d_gp, d_utab, c);
+    PgFLevels lv;
+    for (uint32_t j = 0; j < 3; ++j) { lv.beta[j] = betas[TL + j]; lv.delta[j] = deltas[TL + j]; }
+    {
+        prof::Scope ps("pg_F_leaves", st, S->rows * n_gates);
+        // the reference's leaf rows: the gates at row 0 once, then the leaf pass reads them
+        launch_hoisted(a, compat != 0, 1, tiles_per_gate, [&](uint32_t tiles) { launch_F_leaves(S, a, lv, tiles, T, t.max_slots, cur, (uint32_t)n0, st); });
+    }
+    // remaining leaf-index bits, in the order adjacent nodes differ: thread bits 0 .. TL-1, then tile / gate bits TL+3 ..
+    std::vector<uint32_t> order;
+    for (uint32_t b = 0; b < TL; ++b) order.push_back(b);
+    for (uint32_t b = TL + 3; b < levels; ++b) order.push_back(b);
+    size_t n_in = n0, m_valid = n_tiles_valid * T;
+    uint32_t deg = 3;
+    size_t at = 0;
+    // (dynamic LDS of a launch stays below 48 KiB: degree <= 23 after the launch -- every table size an NTT of <= 2^28 allows; beyond, the r03 flow)
+    while (at < order.size() && deg + std::min<size_t>(PG_F_MULTI_LEVELS, order.size() - at) <= 23) {
+        // up to six levels per launch (k_pg_F_multi); what is left beyond degree 23: one launch per level + the one-workgroup tail
+        const uint32_t nlev = (uint32_t)std::min<size_t>(PG_F_MULTI_LEVELS, order.size() - at);
+        PgFMulti tm;
+        for (uint32_t l = 0; l < PG_F_MULTI_LEVELS; ++l) {
+            tm.beta[l] = l < nlev ? betas[order[at + l]] : Fr::zero();
+            tm.delta[l] = l < nlev ? deltas[order[at + l]] : Fr::zero();
+        }
+        const size_t n_out = n_in >> nlev;
+        const size_t lds = 2 * (size_t)PG_F_MULTI_NODES * (deg + nlev + 1) * sizeof(fe_t);
+        SRS_LAUNCH((k_pg_F_multi<Fr>), ((uint32_t)n_out), (256), lds, st, (const fe_t *)cur, (uint32_t)n_in, (uint32_t)m_valid, deg, nlev, tm, nxt,
+                   (uint32_t)n_out);
+        n_in = n_out;
+        m_valid = (m_valid + (((size_t)1 << nlev) - 1)) >> nlev;
+        deg += nlev;
+        at += nlev;
+        std::swap(cur, nxt);
+    }
+    for (; at < order.size(); ++at) {
+        // the last levels (<= 32 nodes left) run in one workgroup (k_pg_F_tail)
+        const size_t left = order.size() - at;
+        if (n_in <= 32 && left <= PG_F_TAIL_LEVELS && deg + left <= PG_F_TAIL_MAXDEG) break;
+        const uint32_t b = order[at];
+        const size_t n_out = n_in / 2;
+        SRS_LAUNCH((k_pg_F_level<Fr>), ((uint32_t)((n_out * (deg + 2) + 127) / 128)), (128), 0, st, (const fe_t *)cur, (uint32_t)n_in,
+                   (uint32_t)m_valid, deg, betas[b], deltas[b], nxt, (uint32_t)n_out);
+        n_in = n_out;
+        m_valid = (m_valid + 1) / 2;
+        ++deg;
+        std::swap(cur, nxt);
+    }
+    if (at < order.size()) {
+        const uint32_t nlev = (uint32_t)(order.size() - at);
+        PgFTail tl;
+        for (uint32_t l = 0; l < PG_F_TAIL_LEVELS; ++l) {
+            tl.beta[l] = l < nlev ? betas[order[at + l]] : Fr::zero();
+            tl.delta[l] = l < nlev ? deltas[order[at + l]] : Fr::zero();
+        }
+        SRS_LAUNCH((k_pg_F_tail<Fr>), (1), (512), 0, st, (const fe_t *)cur, (uint32_t)n_in, (uint32_t)m_valid, deg, nlev, tl, nxt);
+        deg += nlev;
+        std::swap(cur, nxt);
+    }
+    // n_in == 1: cur[m] = coefficient m, m <= deg = levels; the reference's vector has fft_points_count_F entries
+    std::vector<fe_t> coef(deg + 1);
+    SRS_HIP_CHECK(hipMemcpyAsync(coef.data(), cur, coef.size() * sizeof(fe_t), hipMemcpyDeviceToHost, st));
+    finish(st);
+    for (uint32_t m = 0; m < P_out; ++m) out_host[m] = m < coef.size() ? coef[m] : Fr::zero();
+    return 0;
+}
+
+// the upper levels of the weighted tree over the tile partials in `cur` (m of them, zero padding beyond the m_valid of the real gates)
+// -> the device pointer of the P sums (`cur` or `nxt`)
+static fe_t *pg_reduce(fe_t *cur, fe_t *nxt, size_t m, size_t m_valid, uint32_t P, const fe_t *d_w, uint32_t wpts, uint32_t level0, hipStream_t st) {
+    while (m > 1) {
+        uint32_t lv = std::min<uint32_t>(7, ilog2(m));
+        uint32_t outs = (uint32_t)(m >> lv);
+        if (((size_t)P << lv) <= PG_REDUCE_PAR_THREADS && (((size_t)P << lv) % 64 == 0 || outs == 1))
+            SRS_LAUNCH((k_pg_reduce_par<Fr>), (outs), (1u << lv, P), 0, st, (const fe_t *)cur, (uint32_t)m_valid, P, d_w, wpts, level0, lv, nxt);
+        else
+            SRS_LAUNCH((k_pg_reduce<Fr>), (outs), (1u << lv), 0, st, (const fe_t *)cur, (uint32_t)m_valid, P, d_w, wpts, level0, lv, nxt);
+        level0 += lv;
+        m = outs;
+        m_valid = outs;
+        std::swap(cur, nxt);
+    }
+    return cur;
+}
+
+// Leaves + weighted reduce: compute_G, evaluate_e, and compute_F on small tables or as the cross-check of the tree (tuning pg_f_eval = 1).
+// One leaf launch leaves a partial sum per (tile, point), pg_reduce the P sums; then G / F are interpolated from them.
+static int pg_leaf_sums(Structure *S, int mode, const fe_t *const *W_dev, const fe_t *const *challenges_host, size_t n_ch, size_t J, const fe_t *weights_in,
+                        const fe_t *delta, int compat, const PgSizes &sz, hipStream_t st, fe_t *out_host, uint32_t P_out, size_t *n_out, std::string &err,
+                        const fe_t *g_at_one, PgGValues *keep_on_device) {
+    // compute_G with one incoming trace (L = 1, Lagrange domain {1, -1}): the folded witness L_0(X) w_0 + L_1(X) w_1 =
+    // (w_0 + w_1)/2 + X (w_0 - w_1)/2 is LINEAR in X, so G has degree <= max gate degree d_G.  Instead of the reference's
+    // next_pow2(d_G + 1) roots of unity (2 multiplies per advice load to fold the witness, then an ifft) G is evaluated at
+    // the integers 0..d_G (fold = halvings + additions, d_G + 1 points) and interpolated with the constant inverse
+    // Vandermonde matrix: the same polynomial, hence the same coefficients (exact arithmetic), ~35 % less work.
+    const bool g_int = mode == 1 && J == 2 && tuning::get_or(tuning::PG_G_FFT, 0) == 0;      // (tuning pg_g_fft: the L >= 2 route on L = 1, for the equality test)
+    const uint32_t dG = (uint32_t)S->max_gate_degree;
+    // 8 leaves per thread once a gate has >= 1024 rows: 1024-leaf tiles, the first three tree levels in registers
+    const uint32_t lpt = S->k >= 10 ? PG_LPT : 1u;
+    const uint32_t tile_log = lpt == PG_LPT ? 10u : std::min<uint32_t>(7, S->k);
+    // ... and one of the d_G + 1 values is free for a caller that has F: at X = 1 the fold IS the accumulator (L_0(1) = 1), the
+    // weights are betas_stroke = beta + alpha delta^(2^b), so G(1) = sum_i pow_i(betas_stroke) f_i(acc) = F(alpha) -- an
+    // identity of the definitions, whatever the traces hold.  ProtoGalaxy::prove has F(alpha) (it is compute_K's first
+    // argument): with `g_at_one` the leaves are evaluated at X = 2 .. d_G + 1 only (d_G points), and the interpolation
+    // nodes are 1 .. d_G + 1.  Needs the sweep-form leaf kernel (below); otherwise all d_G + 1 points are evaluated.
+    const bool skip_one = g_int && g_at_one != nullptr && dG >= 2 && S->pg_spec_id >= 0 && lpt == PG_LPT && dG + 1 <= DMAX + 1;
+    const uint32_t pt0 = skip_one ? 2u : 0u;
+    const uint32_t P = g_int ? (skip_one ? dG : dG + 1) : P_out;   // evaluation points actually used
+    const uint32_t leaf_pts = mode == 1 ? P : 1u;
+    const uint32_t wpts = mode == 0 ? P : 1u;
+    const uint32_t levels = (uint32_t)sz.betas_count, n_gates = (uint32_t)S->gate_progs.size();
+    const PgPoints pp = pg_points(g_int, pt0, P, mode == 1, J, (uint32_t)sz.lagrange_domain, challenges_host, n_ch);
+    // ---- weights [levels][wpts]: F's are beta_b + X_p delta^(2^b)  (:102-111)
+    std::vector<fe_t> weights(weights_in, weights_in + levels);
+    if (mode == 0) {
+        const std::vector<fe_t> deltas = pg_deltas(*delta, levels);
+        weights.resize((size_t)levels * P);
+        for (uint32_t b = 0; b < levels; ++b)
+            for (uint32_t p = 0; p < P; ++p) weights[(size_t)b * P + p] = Fr::add(weights_in[b], Fr::mul(pp.pts[p], deltas[b]));
+    }
+    // the specialised leaf kernel in sweep form (k_pg_leaves_sweep): integer-point G and evaluate_e of a known gate set
+    const bool sweep_leaves = S->pg_spec_id >= 0 && lpt == PG_LPT && mode != 0 && (mode != 1 || g_int) && P <= DMAX + 1;
+    PgSlotWeights sw;
+    if (sweep_leaves) sw = pg_slot_weights_leaves(weights.data() + (tile_log - 3));      // (wpts == 1 in sweep form)
+    PgGateTable t;
+    if (int rc = pg_gate_table(S, pp.ch_pt, n_ch, sweep_leaves ? &sw : nullptr, t, err)) return rc;
+    const uint32_t tile = (1u << tile_log) / lpt, tiles_per_gate = (uint32_t)(S->rows >> tile_log);
+    const size_t n_tiles_valid = (size_t)n_gates * tiles_per_gate, n_tiles_padded = sz.count_with_padding >> tile_log;
+    // ---- device staging
+    Arena &A = S->arena;
+    A.reserve(Arena::pad(weights.size() * sizeof(fe_t)) + Arena::pad((pp.wcoef.size() + 1) * sizeof(fe_t)) +
+              Arena::pad((t.utab.size() + 1) * sizeof(fe_t)) + Arena::pad(t.gp.size() * sizeof(GateProg)) +
+              2 * Arena::pad((n_tiles_padded + 1) * P * sizeof(fe_t)) + Arena::pad(sizeof(fe_t) * P) +
+              Arena::pad(((size_t)n_gates * P + 1) * sizeof(fe_t)) + 4096);
+    A.reset();
+    fe_t *d_w = A.take<fe_t>(weights.size());
+    fe_t *d_coef = A.take<fe_t>(pp.wcoef.size() + 1);
+    fe_t *d_utab = A.take<fe_t>(t.utab.size() + 1);
+    GateProg *d_gp = A.take<GateProg>(t.gp.size());
+    fe_t *buf0 = A.take<fe_t>((n_tiles_padded + 1) * P);
+    fe_t *buf1 = A.take<fe_t>((n_tiles_padded + 1) * P);
+    fe_t *d_hoist = A.take<fe_t>((size_t)n_gates * P + 1);
+    SRS_HIP_CHECK(hipMemcpyAsync(d_w, weights.data(), weights.size() * sizeof(fe_t), hipMemcpyHostToDevice, st));
+    if (!pp.wcoef.empty()) SRS_HIP_CHECK(hipMemcpyAsync(d_coef, pp.wcoef.data(), pp.wcoef.size() * sizeof(fe_t), hipMemcpyHostToDevice, st));
+    SRS_HIP_CHECK(hipMemcpyAsync(d_utab, t.utab.data(), t.utab.size() * sizeof(fe_t), hipMemcpyHostToDevice, st));
+    SRS_HIP_CHECK(hipMemcpyAsync(d_gp, t.gp.data(), t.gp.size() * sizeof(GateProg), hipMemcpyHostToDevice, st));
+    PgCall c;
+    c.n_w = J;
+    c.J = (uint32_t)(mode == 1 ? J : 1);
+    c.wcoef = (mode == 1 && !g_int) ? d_coef : nullptr;
+    c.half = g_int ? 1u : 0u;
+    c.pt0 = pt0;
+    c.compat = compat;
+    c.leaf_pts = leaf_pts;
+    c.P = P;
+    c.wpts = wpts;
+    c.tile_log = tile_log;
+    c.weights = d_w;
+    c.partial = buf0;
+    c.hoist = d_hoist;
+    c.sharded = true;
+    PgArgs a = pg_args(S, W_dev, d_gp, d_utab, c);
+    {
+        prof::Scope ps(mode == 0 ? "pg_F_leaves" : (mode == 1 ? "pg_G_leaves" : "pg_e_leaves"), st, S->rows * n_gates);
+        // the reference's leaf rows: the gates at row 0 once per (gate, point) -- the interpreter and the sweep form; the plain ahead-of-time
+        // kernel evaluates per thread -- then the leaf pass runs the weighted trees
+        const bool hoist = compat && (sweep_leaves || !(S->pg_spec_id >= 0 && lpt == PG_LPT));
+        launch_hoisted(a, hoist, leaf_pts, tiles_per_gate, [&](uint32_t tiles) { launch_leaves(S, a, tiles, tile, lpt, t.max_slots, sweep_leaves, st); });
+    }
+    fe_t *sums = pg_reduce(buf0, buf1, n_tiles_padded, n_tiles_valid, P, d_w, wpts, tile_log, st);
+    if (g_int && keep_on_device && dG + 1 <= PG_K_SMALL_MAX_NODES) {      // the caller goes on to K on the device (pg_K_from_G_device): no round trip through the host here
+        keep_on_device->vals_dev = sums;
+        keep_on_device->n_dev = P;
+        keep_on_device->degree = dG;
+        keep_on_device->skip_one = skip_one;
+        *n_out = 0;
+        return 0;
+    }
+    *n_out = P_out;
+    if (g_int) {
+        // G at the nodes 0 .. dG, or 1 .. dG + 1 with G(1) = F(alpha) in front of the evaluated ones
+        std::vector<fe_t> val(dG + 1);
+        if (skip_one) val[0] = *g_at_one;
+        SRS_HIP_CHECK(hipMemcpyAsync(val.data() + (skip_one ? 1 : 0), sums, (size_t)P * sizeof(fe_t), hipMemcpyDeviceToHost, st));
+        finish(st);
+        pg_interpolate(S, val.data(), skip_one ? 1 : 0, out_host, P_out);
+        return 0;
+    }
+    if (mode != 2 && P > 1) ntt::run(sums, ilog2(P), P, 1, true, false, st);      // fft::ifft(&mut points)  (:197, :419)
+    SRS_HIP_CHECK(hipMemcpyAsync(out_host, sums, (size_t)P * sizeof(fe_t), hipMemcpyDeviceToHost, st));
+    finish(st);
+    return 0;
+}
+
 // mode 0: compute_F, 1: compute_G, 2: evaluate_e.  W_dev: J device witness pointers (J = 1 for F / e).
 // challenges_host: J arrays of n_ch challenges.  weights_in: betas (F, e) / betas_stroke (G), betas_count values.
 // out_host: points_F / points_G coefficients (after ifft) or the single value e.
-
 int pg_sum(Structure *S, int mode, const fe_t *const *W_dev, const fe_t *const *challenges_host, size_t n_ch, size_t J,
            const fe_t *weights_in, size_t n_weights, const fe_t *delta, int compat, hipStream_t st, fe_t *out_host,
            size_t *n_out, std::string &err, const fe_t *g_at_one, PgGValues *keep_on_device) {
@@ -1398,381 +1768,60 @@ int pg_sum(Structure *S, int mode, const fe_t *const *W_dev, const fe_t *const *
     PgSizes sz;
     if (!pg_sizes(S, mode == 1 ? J - 1 : 1, sz)) { *n_out = 0; return 0; }
     if (n_weights < sz.betas_count) { err = "not enough betas"; return 4; }
-    FieldOps f{0};
     const uint32_t P_out = mode == 0 ? (uint32_t)sz.points_F : (mode == 1 ? (uint32_t)sz.points_G : 1u);
     if (pg_closed_route(compat)) {
-        // the reference's leaf rows: the gates at row 0 from the device, the sums in closed form on the host.  A row-sharded structure has
-        // nothing to shard here (every rank holds row 0): rank 0 returns the whole polynomial, the others the zero polynomial
-        for (uint32_t m = 0; m < P_out; ++m) out_host[m] = Fr::zero();
         *n_out = P_out;
-        if (S->shard_world > 1 && S->shard_rank != 0) return 0;
-        PgRow0 r0;
-        const int rc = pg_row0_values(S, mode == 1, W_dev, challenges_host, n_ch, J, st, r0, err);
-        if (rc) return rc;
-        const uint32_t n_gates = (uint32_t)S->gate_progs.size(), levels = (uint32_t)sz.betas_count;
-        if (mode == 0) pg_closed_F(r0.vals.data(), n_gates, S->k, weights_in, *delta, levels, out_host, P_out);
-        else if (mode == 1) pg_closed_G(S, r0, weights_in, levels, out_host, P_out);
-        else out_host[0] = pg_closed_sum(r0.vals.data(), 1, n_gates, S->k, weights_in, levels);
-        return 0;
+        return pg_closed(S, mode, W_dev, challenges_host, n_ch, J, weights_in, delta, (uint32_t)sz.betas_count, st, out_host, P_out, err);
     }
-    // compute_G with one incoming trace (L = 1, Lagrange domain {1, -1}): the folded witness L_0(X) w_0 + L_1(X) w_1 =
-    // (w_0 + w_1)/2 + X (w_0 - w_1)/2 is LINEAR in X, so G has degree <= max gate degree d_G.  Instead of the reference's
-    // next_pow2(d_G + 1) roots of unity (2 multiplies per advice load to fold the witness, then an ifft) G is evaluated at
-    // the integers 0..d_G (fold = halvings + additions, d_G + 1 points) and interpolated with the constant inverse
-    // Vandermonde matrix: the same polynomial, hence the same coefficients (exact arithmetic), ~35 % less work.
-    const bool g_int = mode == 1 && J == 2 && tuning::get_or(tuning::PG_G_FFT, 0) == 0;      // (tuning pg_g_fft: the L >= 2 route on L = 1, for the equality test)
-    const uint32_t dG = (uint32_t)S->max_gate_degree;
-    // ... and one of the d_G + 1 values is free for a caller that has F: at X = 1 the fold IS the accumulator (L_0(1) = 1), the
-    // weights are betas_stroke = beta + alpha delta^(2^b), so G(1) = sum_i pow_i(betas_stroke) f_i(acc) = F(alpha) -- an
-    // identity of the definitions, whatever the traces hold.  ProtoGalaxy::prove has F(alpha) (it is compute_K's first
-    // argument): with `g_at_one` the leaves are evaluated at X = 2 .. d_G + 1 only (d_G points), and the interpolation
-    // nodes are 1 .. d_G + 1.  Needs the sweep-form leaf kernel (below); otherwise all d_G + 1 points are evaluated.
-    const uint32_t lpt_probe = S->k >= 10 ? 8u : 1u;
-    const bool skip_one = g_int && g_at_one != nullptr && dG >= 2 && S->pg_spec_id >= 0 && lpt_probe == 8 && dG + 1 <= DMAX + 1 &&
-                          true;
-    const uint32_t pt0 = skip_one ? 2u : 0u;
-    const uint32_t P = g_int ? (skip_one ? dG : dG + 1) : P_out;   // evaluation points actually used
-    const uint32_t leaf_pts = mode == 1 ? P : 1u;
-    const uint32_t wpts = mode == 0 ? P : 1u;
-    const uint32_t levels = (uint32_t)sz.betas_count;
-    const uint32_t n_gates = (uint32_t)S->gate_progs.size();
-    // ---- weights [levels][wpts]
-    std::vector<fe_t> weights((size_t)levels * wpts);
-    std::vector<fe_t> pts;                                     // evaluation points X_p (F: w_t'^p ; G: w_G^p)
-    if (g_int) {
-        for (uint32_t p = 0; p < P; ++p) pts.push_back(Fr::from_u64(pt0 + p));
-    } else if (mode != 2) {
-        fe_t w = ntt::omega(ilog2(P), false), x = Fr::one();
-        for (uint32_t p = 0; p < P; ++p) { pts.push_back(x); x = Fr::mul(x, w); }     // iter_cyclic_subgroup
-    }
-    if (mode == 0) {
-        fe_t d = *delta;                                       // deltas: delta^(2^b)  (:97-99)
-        for (uint32_t b = 0; b < levels; ++b) {
-            for (uint32_t p = 0; p < P; ++p) weights[(size_t)b * P + p] = Fr::add(weights_in[b], Fr::mul(pts[p], d));   // :102-111
-            d = Fr::sqr(d);
-        }
-    } else {
-        for (uint32_t b = 0; b < levels; ++b) weights[b] = weights_in[b];
-    }
-    // ---- witness combination coefficients and per-point challenges
-    std::vector<fe_t> wcoef;                                   // [P][J] = L_j(X_p)   (FoldedWitness::new, folded_witness.rs:20-47)
-    std::vector<std::vector<fe_t>> ch_pt(leaf_pts, std::vector<fe_t>(n_ch ? n_ch : 1, Fr::zero()));
-    if (mode == 1) {
-        wcoef.resize((size_t)P * J);
-        // integer-point G folds the witnesses by halvings in the kernel: L_j(X_p) is only needed to fold challenges
-        for (uint32_t p = 0; p < P && (!g_int || n_ch); ++p) {
-            std::vector<fe_t> L = lagrange_eval(pts[p], (uint32_t)sz.lagrange_domain);
-            for (size_t j = 0; j < J; ++j) {
-                wcoef[(size_t)p * J + j] = L[j];
-                for (size_t c = 0; c < n_ch; ++c)             // fold_plonk_challenges :142-180
-                    ch_pt[p][c] = Fr::add(ch_pt[p][c], Fr::mul(challenges_host[j][c], L[j]));
-            }
-        }
-    } else {
-        for (size_t c = 0; c < n_ch; ++c) ch_pt[0][c] = challenges_host[0][c];
-    }
-    // 8 leaves per thread once a gate has >= 1024 rows: 1024-leaf tiles, the first three tree levels in registers
-    const uint32_t lpt = S->k >= 10 ? 8u : 1u;
-    const uint32_t tile_log = lpt == 8 ? 10u : std::min<uint32_t>(7, S->k);
-    // the specialised leaf kernel in sweep form (k_pg_leaves_sweep): integer-point G and evaluate_e of a known gate set
-    const bool sweep_leaves = S->pg_spec_id >= 0 && lpt == 8 && mode != 0 && (mode != 1 || g_int) && P <= DMAX + 1;
-    // ---- uniform tables per gate / leaf point
-    uint32_t max_slots = 1;
-    std::vector<GateProg> gp(n_gates);
-    std::vector<fe_t> utab;
-    for (uint32_t g = 0; g < n_gates; ++g) {
-        Program &p = S->gate_progs[g];
-        max_slots = std::max(max_slots, p.nslots);
-        const size_t nu = p.uops.size() ? p.uops.size() : 1;
-        gp[g].prog = p.d_insns;
-        gp[g].n_insn = (uint32_t)p.insns.size();
-        gp[g].result = p.result;
-        gp[g].n_uniform = (uint32_t)nu;
-        gp[g].utab_off = (uint32_t)utab.size();
-        utab.resize(utab.size() + nu * leaf_pts * (sweep_leaves ? lpt + 1 : 1u));
-        for (uint32_t lp = 0; lp < leaf_pts; ++lp)
-            if (!eval_uniform(p, f, ch_pt[lp].data(), n_ch, 0, false, 0, utab.data() + gp[g].utab_off + (size_t)lp * nu, err)) return 7;
-        if (sweep_leaves) {
-            // k_pg_leaves_sweep: one table per leaf slot l of a thread, the term coefficients times w_l = prod_{b in bits(l)} c_(TL + b)
-            // table lpt: the SUM of the w_l (reference_compat: the lpt leaves of a thread share one evaluation at row 0)
-            const uint32_t TL = tile_log - 3;
-            fe_t wsum = Fr::one();
-            for (uint32_t l = 1; l <= lpt; ++l) {
-                fe_t wl = Fr::one();
-                for (uint32_t b = 0; b < 3; ++b)
-                    if ((l >> b) & 1u) wl = Fr::mul(wl, weights[(size_t)(TL + b) * wpts]);
-                if (l == lpt) wl = wsum; else wsum = Fr::add(wsum, wl);
-                fe_t *dst = utab.data() + gp[g].utab_off + (size_t)l * leaf_pts * nu;
-                std::memcpy(dst, utab.data() + gp[g].utab_off, (size_t)leaf_pts * nu * sizeof(fe_t));
-                for (uint32_t lp = 0; lp < leaf_pts; ++lp)
-                    for (int ci : p.sw_coef) dst[(size_t)lp * nu + ci] = Fr::mul(dst[(size_t)lp * nu + ci], wl);
-            }
-        }
-    }
-    if (max_slots > 32) { err = "row program needs more than 32 live registers"; return 4; }
-    const uint32_t tile = (1u << tile_log) / lpt, tiles_per_gate = (uint32_t)(S->rows >> tile_log);
-    const size_t n_tiles_valid = (size_t)n_gates * tiles_per_gate;
-    const size_t n_tiles_padded = sz.count_with_padding >> tile_log;
-    // ---- compute_F with >= 1024 rows per gate: polynomial tree (see k_pg_F_leaves); the evaluate-and-interpolate route
-    //      below stays for small tables and as the cross-check (tuning pg_f_eval = 1)
-    if (mode == 0 && lpt == 8 && tuning::get_or(tuning::PG_F_EVAL, 0) == 0) {
-        const uint32_t TL = tile_log - 3, T = tile;
-        const size_t n0 = n_tiles_padded * T;
-        Arena &A = S->arena;
-        A.reserve(2 * Arena::pad((4 * n0 + 64) * sizeof(fe_t)) + Arena::pad((utab.size() + 1) * sizeof(fe_t)) +
-                  Arena::pad(gp.size() * sizeof(GateProg)) + Arena::pad((n_gates + 1) * sizeof(fe_t)) + 4096);
-        A.reset();
-        fe_t *d_utab = A.take<fe_t>(utab.size() + 1);
-        GateProg *d_gp = A.take<GateProg>(gp.size());
-        fe_t *cur = A.take<fe_t>(4 * n0 + 64), *nxt = A.take<fe_t>(4 * n0 + 64);
-        fe_t *d_hoist = A.take<fe_t>(n_gates + 1);
-        SRS_HIP_CHECK(hipMemcpyAsync(d_utab, utab.data(), utab.size() * sizeof(fe_t), hipMemcpyHostToDevice, st));
-        SRS_HIP_CHECK(hipMemcpyAsync(d_gp, gp.data(), gp.size() * sizeof(GateProg), hipMemcpyHostToDevice, st));
-        std::vector<fe_t> deltas(levels);
-        {
-            fe_t d = *delta;                                   // deltas: delta^(2^b)  (:97-99)
-            for (uint32_t b = 0; b < levels; ++b) { deltas[b] = d; d = Fr::sqr(d); }
-        }
-        PgArgs a;
-        a.gates = d_gp;
-        a.n_gates = n_gates;
-        a.log_rows = S->k;
-        a.ctx.rows = (uint32_t)S->rows;
-        a.ctx.sel = S->d_sel_ptrs;
-        a.ctx.fix = S->d_fix_ptrs;
-        for (uint32_t j = 0; j < JMAX; ++j) a.ctx.W[j] = j < 1 ? W_dev[j] : nullptr;
-        a.ctx.J = 1;
-        a.ctx.wcoef = nullptr;
-        a.ctx.half = 0;
-        a.ctx.pt0 = 0;
-        a.ctx.shard_rank = 0;
-        a.ctx.shard_world = 1;
-        a.ctx.local_rows = a.ctx.rows;
-        a.compat = compat;
-        a.leaf_pts = 1;
-        a.P = 1;
-        a.utab = d_utab;
-        a.weights = nullptr;
-        a.wpts = 1;
-        a.tile_log = tile_log;
-        a.partial = nullptr;
-        a.shard_rank = S->shard_rank;                      // lpt == 8 here: tile_log == STRIPE_LOG
-        a.shard_world = S->shard_world;
-        a.hoist = d_hoist;
-        a.hoist_mode = 0;
-        PgFLevels lv;
-        for (uint32_t j = 0; j < 3; ++j) { lv.beta[j] = weights_in[TL + j]; lv.delta[j] = deltas[TL + j]; }
-        {
-            prof::Scope ps("pg_F_leaves", st, S->rows * n_gates);
-            auto leaves = [&](uint32_t tiles) {
-                if (S->pg_spec_id == 0) SRS_LAUNCH((k_pg_F_leaves<Fr, 2, 0>), (tiles, n_gates), (T), 0, st, a, lv, cur, (uint32_t)n0);
-                else if (max_slots <= 8) SRS_LAUNCH((k_pg_F_leaves<Fr, 8, -1>), (tiles, n_gates), (T), 0, st, a, lv, cur, (uint32_t)n0);
-                else if (max_slots <= 16) SRS_LAUNCH((k_pg_F_leaves<Fr, 16, -1>), (tiles, n_gates), (T), 0, st, a, lv, cur, (uint32_t)n0);
-                else SRS_LAUNCH((k_pg_F_leaves<Fr, 32, -1>), (tiles, n_gates), (T), 0, st, a, lv, cur, (uint32_t)n0);
-            };
-            if (compat) {                                  // the gates at row 0 once, then the leaf pass reads them
-                a.hoist_mode = 1;
-                leaves(1);
-                a.hoist_mode = 2;
-            }
-            leaves(tiles_per_gate);
-        }
-        // remaining leaf-index bits, in the order adjacent nodes differ: thread bits 0 .. TL-1, then tile / gate bits TL+3 ..
-        std::vector<uint32_t> order;
-        for (uint32_t b = 0; b < TL; ++b) order.push_back(b);
-        for (uint32_t b = TL + 3; b < levels; ++b) order.push_back(b);
-        size_t n_in = n0, m_valid = n_tiles_valid * T;
-        uint32_t deg = 3;
-        size_t at = 0;
-        // (dynamic LDS of a launch stays below 48 KiB: degree <= 23 after the launch -- every table size an NTT of <= 2^28 allows; beyond, the r03 flow)
-        while (at < order.size() && deg + std::min<size_t>(PG_F_MULTI_LEVELS, order.size() - at) <= 23) {
-            // up to six levels per launch (k_pg_F_multi); what is left beyond degree 23: one launch per level + the one-workgroup tail
-            const uint32_t nlev = (uint32_t)std::min<size_t>(PG_F_MULTI_LEVELS, order.size() - at);
-            PgFMulti tm;
-            for (uint32_t l = 0; l < PG_F_MULTI_LEVELS; ++l) {
-                tm.beta[l] = l < nlev ? weights_in[order[at + l]] : Fr::zero();
-                tm.delta[l] = l < nlev ? deltas[order[at + l]] : Fr::zero();
-            }
-            const size_t n_out = n_in >> nlev;
-            const size_t lds = 2 * (size_t)PG_F_MULTI_NODES * (deg + nlev + 1) * sizeof(fe_t);
-            SRS_LAUNCH((k_pg_F_multi<Fr>), ((uint32_t)n_out), (256), lds, st, (const fe_t *)cur, (uint32_t)n_in, (uint32_t)m_valid, deg, nlev, tm, nxt,
-                       (uint32_t)n_out);
-            n_in = n_out;
-            m_valid = (m_valid + (((size_t)1 << nlev) - 1)) >> nlev;
-            deg += nlev;
-            at += nlev;
-            std::swap(cur, nxt);
-        }
-        for (; at < order.size(); ++at) {
-            // the last levels (<= 32 nodes left) run in one workgroup (k_pg_F_tail)
-            const size_t left = order.size() - at;
-            if (n_in <= 32 && left <= PG_F_TAIL_LEVELS && deg + left <= PG_F_TAIL_MAXDEG) break;
-            const uint32_t b = order[at];
-            const size_t n_out = n_in / 2;
-            SRS_LAUNCH((k_pg_F_level<Fr>), ((uint32_t)((n_out * (deg + 2) + 127) / 128)), (128), 0, st, (const fe_t *)cur, (uint32_t)n_in,
-                       (uint32_t)m_valid, deg, weights_in[b], deltas[b], nxt, (uint32_t)n_out);
-            n_in = n_out;
-            m_valid = (m_valid + 1) / 2;
-            ++deg;
-            std::swap(cur, nxt);
-        }
-        if (at < order.size()) {
-            const uint32_t nlev = (uint32_t)(order.size() - at);
-            PgFTail tl;
-            for (uint32_t l = 0; l < PG_F_TAIL_LEVELS; ++l) {
-                tl.beta[l] = l < nlev ? weights_in[order[at + l]] : Fr::zero();
-                tl.delta[l] = l < nlev ? deltas[order[at + l]] : Fr::zero();
-            }
-            SRS_LAUNCH((k_pg_F_tail<Fr>), (1), (512), 0, st, (const fe_t *)cur, (uint32_t)n_in, (uint32_t)m_valid, deg, nlev, tl, nxt);
-            deg += nlev;
-            std::swap(cur, nxt);
-        }
-        // n_in == 1: cur[m] = coefficient m, m <= deg = levels; the reference's vector has fft_points_count_F entries
-        std::vector<fe_t> coef(deg + 1);
-        SRS_HIP_CHECK(hipMemcpyAsync(coef.data(), cur, coef.size() * sizeof(fe_t), hipMemcpyDeviceToHost, st));
-        SRS_HIP_CHECK(hipStreamSynchronize(st));
-        SRS_HIP_CHECK(hipGetLastError());
-        prof::collect();
-        for (uint32_t m = 0; m < P; ++m) out_host[m] = m < coef.size() ? coef[m] : Fr::zero();
-        *n_out = P;
-        return 0;
-    }
-    // ---- device staging
-    Arena &A = S->arena;
-    size_t need = Arena::pad(weights.size() * sizeof(fe_t)) + Arena::pad((wcoef.size() + 1) * sizeof(fe_t)) +
-                  Arena::pad((utab.size() + 1) * sizeof(fe_t)) + Arena::pad(gp.size() * sizeof(GateProg)) +
-                  2 * Arena::pad((n_tiles_padded + 1) * P * sizeof(fe_t)) + Arena::pad(sizeof(fe_t) * P) +
-                  Arena::pad(((size_t)n_gates * P + 1) * sizeof(fe_t)) + 4096;
-    A.reserve(need);
-    A.reset();
-    fe_t *d_w = A.take<fe_t>(weights.size());
-    fe_t *d_coef = A.take<fe_t>(wcoef.size() + 1);
-    fe_t *d_utab = A.take<fe_t>(utab.size() + 1);
-    GateProg *d_gp = A.take<GateProg>(gp.size());
-    fe_t *buf0 = A.take<fe_t>((n_tiles_padded + 1) * P);
-    fe_t *buf1 = A.take<fe_t>((n_tiles_padded + 1) * P);
-    fe_t *d_hoist = A.take<fe_t>((size_t)n_gates * P + 1);
-    SRS_HIP_CHECK(hipMemcpyAsync(d_w, weights.data(), weights.size() * sizeof(fe_t), hipMemcpyHostToDevice, st));
-    if (!wcoef.empty()) SRS_HIP_CHECK(hipMemcpyAsync(d_coef, wcoef.data(), wcoef.size() * sizeof(fe_t), hipMemcpyHostToDevice, st));
-    SRS_HIP_CHECK(hipMemcpyAsync(d_utab, utab.data(), utab.size() * sizeof(fe_t), hipMemcpyHostToDevice, st));
-    SRS_HIP_CHECK(hipMemcpyAsync(d_gp, gp.data(), gp.size() * sizeof(GateProg), hipMemcpyHostToDevice, st));
-    PgArgs a;
-    a.gates = d_gp;
-    a.n_gates = n_gates;
-    a.log_rows = S->k;
-    a.ctx.rows = (uint32_t)S->rows;
-    a.ctx.sel = S->d_sel_ptrs;
-    a.ctx.fix = S->d_fix_ptrs;
-    for (uint32_t j = 0; j < JMAX; ++j) a.ctx.W[j] = j < J ? W_dev[j] : nullptr;
-    a.ctx.J = (uint32_t)(mode == 1 ? J : 1);
-    a.ctx.wcoef = (mode == 1 && !g_int) ? d_coef : nullptr;
-    a.ctx.half = g_int ? 1u : 0u;
-    a.ctx.shard_rank = 0;
-    a.ctx.shard_world = 1;
-    a.ctx.local_rows = a.ctx.rows;
-    a.ctx.pt0 = pt0;
-    a.compat = compat;
-    a.leaf_pts = leaf_pts;
-    a.P = P;
-    a.utab = d_utab;
-    a.weights = d_w;
-    a.wpts = wpts;
-    a.tile_log = tile_log;
-    a.partial = buf0;
-    // partial sums of a sharded structure: by tiles when a tile is a stripe (k >= 10), else rank 0 evaluates everything
-    if (tile_log == STRIPE_LOG) { a.shard_rank = S->shard_rank; a.shard_world = S->shard_world; }
-    else if (S->shard_world > 1 && S->shard_rank != 0) { a.shard_rank = 0xFFFFFFFFu; a.shard_world = 2; }     // no tile is mine
-    else { a.shard_rank = 0; a.shard_world = 1; }
-    {
-        prof::Scope ps(mode == 0 ? "pg_F_leaves" : (mode == 1 ? "pg_G_leaves" : "pg_e_leaves"), st, S->rows * n_gates);
-        a.hoist = d_hoist;
-        a.hoist_mode = 0;
-        if (S->pg_spec_id >= 0 && lpt == 8) {
-            if (sweep_leaves && compat) {     // k_pg_leaves_sweep<.., COMPAT>: the gates at row 0 once, then the leaf pass
-                a.hoist_mode = 1;
-                launch_pg_spec(S->pg_spec_id, a, P, n_gates, tile, st, sweep_leaves);      // one workgroup per (point, gate)
-                a.hoist_mode = 2;
-            }
-            launch_pg_spec(S->pg_spec_id, a, tiles_per_gate, n_gates, tile, st, sweep_leaves);
-        }
-        else {
-            auto leaves = [&](uint32_t tiles) {
-                if (max_slots <= 8) launch_pg_leaves<8>(a, tiles, n_gates, tile, lpt, st);
-                else if (max_slots <= 12) launch_pg_leaves<12>(a, tiles, n_gates, tile, lpt, st);
-                else if (max_slots <= 16) launch_pg_leaves<16>(a, tiles, n_gates, tile, lpt, st);
-                else launch_pg_leaves<32>(a, tiles, n_gates, tile, lpt, st);
-            };
-            if (compat) {                      // the interpreter too evaluates the gates at row 0 once per (gate, point), then runs the weighted trees
-                a.hoist_mode = 1;
-                leaves(leaf_pts);
-                a.hoist_mode = 2;
-            }
-            leaves(tiles_per_gate);
-        }
-    }
-    // ---- upper levels of the tree over the tile partials (zero padding beyond the real gates)
-    size_t m_valid = n_tiles_valid, m = n_tiles_padded;
-    uint32_t level0 = tile_log;
-    fe_t *cur = buf0, *nxt = buf1;
-    while (m > 1) {
-        uint32_t lv = std::min<uint32_t>(7, ilog2(m));
-        uint32_t outs = (uint32_t)(m >> lv);
-        if (((size_t)P << lv) <= PG_REDUCE_PAR_THREADS && (((size_t)P << lv) % 64 == 0 || outs == 1))
-            SRS_LAUNCH((k_pg_reduce_par<Fr>), (outs), (1u << lv, P), 0, st, (const fe_t *)cur, (uint32_t)m_valid, P, (const fe_t *)d_w, wpts,
-                       level0, lv, nxt);
-        else
-        SRS_LAUNCH((k_pg_reduce<Fr>), (outs), (1u << lv), 0, st, (const fe_t *)cur, (uint32_t)m_valid, P, (const fe_t *)d_w, wpts,
-                   level0, lv, nxt);
-        level0 += lv;
-        m = outs;
-        m_valid = outs;
-        std::swap(cur, nxt);
-    }
-    if (g_int && keep_on_device && dG + 1 <= PG_K_SMALL_MAX_NODES) {      // the caller goes on to K on the device (pg_K_from_G_device): no round trip through the host here
-        keep_on_device->vals_dev = cur;
-        keep_on_device->n_dev = P;
-        keep_on_device->degree = dG;
-        keep_on_device->skip_one = skip_one;
-        *n_out = 0;
-        return 0;
-    }
-    if (g_int) {
-        std::vector<fe_t> val(P);
-        SRS_HIP_CHECK(hipMemcpyAsync(val.data(), cur, (size_t)P * sizeof(fe_t), hipMemcpyDeviceToHost, st));
-        SRS_HIP_CHECK(hipStreamSynchronize(st));
-        SRS_HIP_CHECK(hipGetLastError());
-        prof::collect();
-        for (uint32_t m = 0; m < P_out; ++m) out_host[m] = Fr::zero();
-        if (skip_one) {                                          // values at the nodes 1 .. dG + 1: G(1) = F(alpha), then the evaluated ones
-            std::vector<fe_t> at(dG + 1);
-            at[0] = *g_at_one;
-            for (uint32_t j = 0; j < P; ++j) at[j + 1] = val[j];
-            const std::vector<fe_t> vall = !S->vinv_g1.empty() ? S->vinv_g1 : inverse_vandermonde_at(f, dG, 1);   // [dG + 1][dG + 1], rows k = 0..dG
-            for (uint32_t k = 0; k <= dG && k < P_out; ++k) {
-                fe_t acc = Fr::zero();
-                for (uint32_t j = 0; j <= dG; ++j) acc = Fr::add(acc, Fr::mul(vall[(size_t)k * (dG + 1) + j], at[j]));
-                out_host[k] = acc;
-            }
-            *n_out = P_out;
-            return 0;
-        }
-        const std::vector<fe_t> vinv = !S->vinv_g.empty() ? S->vinv_g : (dG ? inverse_vandermonde_rows(f, dG) : std::vector<fe_t>());    // [dG][dG + 1], rows k = 1..dG
-        out_host[0] = val[0];                                                                       // G(0)
-        for (uint32_t k = 1; k <= dG && k < P_out; ++k) {
-            fe_t acc = Fr::zero();
-            for (uint32_t j = 0; j < P; ++j) acc = Fr::add(acc, Fr::mul(vinv[(size_t)(k - 1) * P + j], val[j]));
-            out_host[k] = acc;
-        }
+    // the evaluate-and-interpolate route of compute_F stays for small tables and as the cross-check (tuning pg_f_eval = 1)
+    if (mode == 0 && S->k >= 10 && tuning::get_or(tuning::PG_F_EVAL, 0) == 0) {
         *n_out = P_out;
-        return 0;
+        return pg_F_tree(S, W_dev, challenges_host, n_ch, weights_in, *delta, compat, sz, st, out_host, P_out, err);
     }
-    if (mode != 2 && P > 1) ntt::run(cur, ilog2(P), P, 1, true, false, st);      // fft::ifft(&mut points)  (:197, :419)
-    SRS_HIP_CHECK(hipMemcpyAsync(out_host, cur, (size_t)P * sizeof(fe_t), hipMemcpyDeviceToHost, st));
-    SRS_HIP_CHECK(hipStreamSynchronize(st));
-    SRS_HIP_CHECK(hipGetLastError());
-    prof::collect();
-    *n_out = P;
-    return 0;
+    return pg_leaf_sums(S, mode, W_dev, challenges_host, n_ch, J, weights_in, delta, compat, sz, st, out_host, P_out, n_out, err, g_at_one, keep_on_device);
+}
+
+// compute_K_from_G's small domain (256 points in every configuration, quirk Q2).  Everything that depends on the domain only -- the points
+// X_i = zeta omega^i, L_0(X_i) = Z(X_i) / (n (X_i - 1)) (lagrange.rs:50-75) and 1 / Z(X_i) -- is computed once per (domain, n) with ONE inversion
+// for all denominators (Montgomery's trick) and kept: tab = [xs | l0 | inv_z], count each.  zero_z: some Z(X_i) = 0, no l0 / inv_z
+struct KDomain { std::vector<fe_t> tab; bool zero_z = false; };
+static const KDomain &k_domain_table(uint32_t log_domain_K, size_t instances_to_fold) {
+    static std::mutex mu;
+    static std::map<std::pair<uint32_t, size_t>, KDomain> cache;
+    std::lock_guard<std::mutex> lk(mu);
+    auto it = cache.find({log_domain_K, instances_to_fold});
+    if (it != cache.end()) return it->second;
+    const size_t count = (size_t)1 << log_domain_K;
+    KDomain d;
+    const fe_t zeta = ntt::zeta(), omega = ntt::omega(log_domain_K, false), one = Fr::one();
+    const fe_t inv_n = Fr::inv(Fr::from_u64(instances_to_fold));
+    d.tab.resize(3 * count);
+    fe_t *xs = d.tab.data(), *l0 = xs + count, *inv_z = l0 + count;
+    std::vector<fe_t> xn1(count), xm1(count), pref(2 * count);
+    fe_t X = zeta, acc = one;
+    for (size_t i = 0; i < count; ++i) { xs[i] = X; X = Fr::mul(X, omega); }
+    for (size_t i = 0; i < count; ++i) {
+        xn1[i] = Fr::sub(Fr::pow_u64(xs[i], instances_to_fold), one);
+        xm1[i] = Fr::sub(xs[i], one);
+        if (Fr::is_zero(xn1[i])) d.zero_z = true;                                  // X = 1 included (then X - 1 = 0 too)
+    }
+    if (!d.zero_z) {
+        for (size_t i = 0; i < count; ++i) {
+            pref[2 * i] = acc;
+            acc = Fr::mul(acc, xn1[i]);
+            pref[2 * i + 1] = acc;
+            acc = Fr::mul(acc, xm1[i]);
+        }
+        fe_t inv = Fr::inv(acc);
+        for (size_t i = count; i-- > 0;) {
+            const fe_t inv_xm1 = Fr::mul(inv, pref[2 * i + 1]);
+            inv = Fr::mul(inv, xm1[i]);
+            inv_z[i] = Fr::mul(inv, pref[2 * i]);
+            inv = Fr::mul(inv, xn1[i]);
+            l0[i] = Fr::mul(inv_n, Fr::mul(xn1[i], inv_xm1));
+        }
+    }
+    return cache.emplace(std::make_pair(log_domain_K, instances_to_fold), std::move(d)).first->second;      // (map nodes do not move)
 }
 
 // compute_K_from_G (src/nifs/protogalaxy/poly/mod.rs:475-509)
@@ -1787,59 +1836,18 @@ int pg_K_from_G(const fe_t *polyG_host, size_t nG, const fe_t &f_alpha, size_t i
     int *d_err = scratch.take<int>(1);
     int herr = 0;
     if (count <= 4096) {
-        // The K domain is tiny (256 points in every configuration, quirk Q2): the points are computed on the host with ONE
-        // inversion for all denominators (Montgomery's trick).  A GPU thread per point spends two Fermat inversions =
-        // 760 dependent multiplications = 0.6 ms of pure latency on it.
-        // Everything that depends on the domain only -- the points X_i = zeta omega^i, 1 / Z(X_i) and L_0(X_i) = Z(X_i) / (n (X_i - 1))
-        // (lagrange.rs:50-75) -- is computed once per (domain, n) and kept: two inversions and 2 x 256 products less per prove.
-        struct KDomain { std::vector<fe_t> xs, l0, inv_z; bool zero_z = false; };
-        static std::mutex mu;
-        static std::map<std::pair<uint32_t, size_t>, KDomain> cache;
-        const KDomain *dom;
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            auto it = cache.find({log_domain_K, instances_to_fold});
-            if (it == cache.end()) {
-                KDomain d;
-                const fe_t zeta = ntt::zeta(), omega = ntt::omega(log_domain_K, false), one = Fr::one();
-                const fe_t inv_n = Fr::inv(Fr::from_u64(instances_to_fold));
-                d.xs.resize(count); d.l0.resize(count); d.inv_z.resize(count);
-                std::vector<fe_t> xn1(count), xm1(count), pref(2 * count);
-                fe_t X = zeta, acc = one;
-                for (size_t i = 0; i < count; ++i) { d.xs[i] = X; X = Fr::mul(X, omega); }
-                for (size_t i = 0; i < count; ++i) {
-                    xn1[i] = Fr::sub(Fr::pow_u64(d.xs[i], instances_to_fold), one);
-                    xm1[i] = Fr::sub(d.xs[i], one);
-                    if (Fr::is_zero(xn1[i])) d.zero_z = true;                                  // X = 1 included (then X - 1 = 0 too)
-                }
-                if (!d.zero_z) {
-                    for (size_t i = 0; i < count; ++i) {
-                        pref[2 * i] = acc;
-                        acc = Fr::mul(acc, xn1[i]);
-                        pref[2 * i + 1] = acc;
-                        acc = Fr::mul(acc, xm1[i]);
-                    }
-                    fe_t inv = Fr::inv(acc);
-                    for (size_t i = count; i-- > 0;) {
-                        const fe_t inv_xm1 = Fr::mul(inv, pref[2 * i + 1]);
-                        inv = Fr::mul(inv, xm1[i]);
-                        d.inv_z[i] = Fr::mul(inv, pref[2 * i]);
-                        inv = Fr::mul(inv, xn1[i]);
-                        d.l0[i] = Fr::mul(inv_n, Fr::mul(xn1[i], inv_xm1));
-                    }
-                }
-                it = cache.emplace(std::make_pair(log_domain_K, instances_to_fold), std::move(d)).first;
-            }
-            dom = &it->second;
-        }
-        if (dom->zero_z) { err = "Z(X) must be not equal to 0"; return 4; }
+        // The K domain is tiny: the points are computed on the host from the kept table.  A GPU thread per point spends two Fermat
+        // inversions = 760 dependent multiplications = 0.6 ms of pure latency on it.
+        const KDomain &dom = k_domain_table(log_domain_K, instances_to_fold);
+        if (dom.zero_z) { err = "Z(X) must be not equal to 0"; return 4; }
+        const fe_t *xs = dom.tab.data(), *l0 = xs + count, *inv_z = l0 + count;
         std::vector<fe_t> kp(count);
         // 256 x (nG Horner steps + 2 products) = ~3 k field products = ~0.1 ms on one core: less than starting helper threads
         // costs (the r01 / early r02 version spawned 8 std::threads per call: 0.2 ms of the gap after compute_G)
         for (size_t i = 0; i < count; ++i) {
             fe_t gi = Fr::zero();
-            for (size_t k = nG; k-- > 0;) gi = Fr::add(Fr::mul(gi, dom->xs[i]), polyG_host[k]);   // UnivariatePoly::eval (univariate.rs:67-75), Horner: same value
-            kp[i] = Fr::mul(Fr::sub(gi, Fr::mul(f_alpha, dom->l0[i])), dom->inv_z[i]);
+            for (size_t k = nG; k-- > 0;) gi = Fr::add(Fr::mul(gi, xs[i]), polyG_host[k]);   // UnivariatePoly::eval (univariate.rs:67-75), Horner: same value
+            kp[i] = Fr::mul(Fr::sub(gi, Fr::mul(f_alpha, l0[i])), inv_z[i]);
         }
         SRS_HIP_CHECK(hipMemcpyAsync(d_out, kp.data(), count * sizeof(fe_t), hipMemcpyHostToDevice, st));
         ntt::run(d_out, log_domain_K, count, 1, true, true, st);     // UnivariatePoly::coset_ifft
@@ -1860,51 +1868,24 @@ int pg_K_from_G(const fe_t *polyG_host, size_t nG, const fe_t &f_alpha, size_t i
     return 0;
 }
 
-// the small K domain's points X_i = zeta omega^i, L_0(X_i) and 1 / Z(X_i) on the device ([xs | l0 | inv_z]), per (domain, n, device)
+// the host's table of the small K domain on the device, per (domain, n, device); nullptr with zero_z
 static const fe_t *k_domain_table_dev(uint32_t log_domain_K, size_t instances_to_fold, bool &zero_z) {
-    struct Tab { fe_t *dev = nullptr; bool zero_z = false; };
     static std::mutex mu;
-    static std::map<std::tuple<int, uint32_t, size_t>, Tab> cache;
+    static std::map<std::tuple<int, uint32_t, size_t>, fe_t *> cache;
+    const KDomain &dom = k_domain_table(log_domain_K, instances_to_fold);
+    zero_z = dom.zero_z;
+    if (zero_z) return nullptr;
     int device = 0;
     SRS_HIP_CHECK(hipGetDevice(&device));
     std::lock_guard<std::mutex> lk(mu);
-    auto key = std::make_tuple(device, log_domain_K, instances_to_fold);
-    auto it = cache.find(key);
-    if (it == cache.end()) {
-        const size_t count = (size_t)1 << log_domain_K;
-        std::vector<fe_t> h(3 * count), xn1(count), xm1(count), pref(2 * count);
-        const fe_t zeta = ntt::zeta(), omega = ntt::omega(log_domain_K, false), one = Fr::one();
-        const fe_t inv_n = Fr::inv(Fr::from_u64(instances_to_fold));
-        Tab t;
-        fe_t X = zeta, acc = one;
-        for (size_t i = 0; i < count; ++i) { h[i] = X; X = Fr::mul(X, omega); }
-        for (size_t i = 0; i < count; ++i) {
-            xn1[i] = Fr::sub(Fr::pow_u64(h[i], instances_to_fold), one);
-            xm1[i] = Fr::sub(h[i], one);
-            if (Fr::is_zero(xn1[i])) t.zero_z = true;
-        }
-        if (!t.zero_z) {                                   // one inversion for all denominators (Montgomery's trick), as the host route
-            for (size_t i = 0; i < count; ++i) {
-                pref[2 * i] = acc;
-                acc = Fr::mul(acc, xn1[i]);
-                pref[2 * i + 1] = acc;
-                acc = Fr::mul(acc, xm1[i]);
-            }
-            fe_t inv = Fr::inv(acc);
-            for (size_t i = count; i-- > 0;) {
-                const fe_t inv_xm1 = Fr::mul(inv, pref[2 * i + 1]);
-                inv = Fr::mul(inv, xm1[i]);
-                h[2 * count + i] = Fr::mul(inv, pref[2 * i]);
-                inv = Fr::mul(inv, xn1[i]);
-                h[count + i] = Fr::mul(inv_n, Fr::mul(xn1[i], inv_xm1));
-            }
-            SRS_HIP_CHECK(hipMalloc((void **)&t.dev, 3 * count * sizeof(fe_t)));        // kept for the life of the process (24 KiB per domain)
-            SRS_HIP_CHECK(hipMemcpy(t.dev, h.data(), 3 * count * sizeof(fe_t), hipMemcpyHostToDevice));
-        }
-        it = cache.emplace(key, t).first;
+    fe_t *&dev = cache[std::make_tuple(device, log_domain_K, instances_to_fold)];
+    if (!dev) {
+        fe_t *d = nullptr;
+        SRS_HIP_CHECK(hipMalloc((void **)&d, dom.tab.size() * sizeof(fe_t)));        // kept for the life of the process (24 KiB per domain)
+        SRS_HIP_CHECK(hipMemcpy(d, dom.tab.data(), dom.tab.size() * sizeof(fe_t), hipMemcpyHostToDevice));
+        dev = d;
     }
-    zero_z = it->second.zero_z;
-    return it->second.dev;
+    return dev;
 }
 
 bool pg_K_device_ok(const PgGValues &g, uint32_t log_domain_K) {
@@ -1920,15 +1901,7 @@ int pg_K_from_G_device(Structure *S, const PgGValues &g, const fe_t &f_alpha, si
     if (zero_z) { err = "Z(X) must be not equal to 0"; return 4; }
     fe_t *&M = S->d_kM[g.skip_one ? 1 : 0];
     if (!M) {
-        FieldOps f{0};
-        std::vector<fe_t> full((size_t)n_nodes * n_nodes);
-        if (g.skip_one) {
-            full = !S->vinv_g1.empty() ? S->vinv_g1 : inverse_vandermonde_at(f, g.degree, 1);                   // [d + 1][d + 1], nodes 1 .. d + 1
-        } else {
-            const std::vector<fe_t> rows = !S->vinv_g.empty() ? S->vinv_g : (g.degree ? inverse_vandermonde_rows(f, g.degree) : std::vector<fe_t>());
-            for (uint32_t j = 0; j < n_nodes; ++j) full[j] = j == 0 ? Fr::one() : Fr::zero();                       // coefficient 0 = G(0)
-            for (size_t i = 0; i < rows.size(); ++i) full[n_nodes + i] = rows[i];                                    // rows k = 1 .. d, nodes 0 .. d
-        }
+        const std::vector<fe_t> full = pg_node_matrix(S, g.degree, g.skip_one ? 1 : 0);
         SRS_HIP_CHECK(hipMalloc((void **)&M, full.size() * sizeof(fe_t)));
         S->owned.push_back(M);
         SRS_HIP_CHECK(hipMemcpy(M, full.data(), full.size() * sizeof(fe_t), hipMemcpyHostToDevice));
@@ -1942,9 +1915,7 @@ int pg_K_from_G_device(Structure *S, const PgGValues &g, const fe_t &f_alpha, si
                n_nodes, f_alpha, tab, count, d_out);
     ntt::run(d_out, log_domain_K, count, 1, true, true, st);     // UnivariatePoly::coset_ifft
     SRS_HIP_CHECK(hipMemcpyAsync(out_host, d_out, (size_t)count * sizeof(fe_t), hipMemcpyDeviceToHost, st));
-    SRS_HIP_CHECK(hipStreamSynchronize(st));
-    SRS_HIP_CHECK(hipGetLastError());
-    prof::collect();
+    finish(st);
     return 0;
 }
 
