@@ -427,6 +427,39 @@ int srs_lookup_coeff_1(srs_structure *S, const srs_fe *advice, const srs_fe *r, 
 int srs_lookup_coeff_2(int field, const srs_fe *l, const srs_fe *t, const srs_fe *m, const srs_fe *r, size_t n,
                        int space, void *stream, srs_fe *h, srs_fe *g);
 int srs_is_sat_log_derivative(srs_structure *S, const srs_fe *W, int space, void *stream, size_t *mismatch_count);
+/* ---- trace generation: PlonkStructure::run_sps_protocol (src/plonk/mod.rs:413-428) as ONE call ----
+ * Dispatches on srs_structure_num_challenges as :421-427 does: 0 -> _0 (:433-457), 1 -> _1 (:465-495), 2 -> _2 (:503-574: lookups
+ * without a vector lookup, the lookup / table polynomials evaluated with r = 0), 3 -> _3 (:581-662); anything else ->
+ * SRS_ERR_UNSUPPORTED ("UnsupportedChallengesCount").
+ *   columns / lens  the n_columns == num_advice advice columns, host vectors (SRS_SPACE_HOST: what try_collect_witness leaves
+ *                   behind) or device vectors; each is padded with zeros to 2^k (concatenate_with_padding).  A device column may
+ *                   already lie at its place in W_dev; it must not overlap W_dev otherwise.
+ *   W_dev           DEVICE, srs_structure_num_witness_columns * 2^k elements: receives the rounds back to back in the layout described
+ *                   at srs_structure_create_lookup, W[0] || W[1] (|| W[2]), grouped as the reference concatenates them --
+ *                   advice || ls || ts || ms and hs || gs (concat_vec!, :520-527, :550-553, :618-621, :636-639).  The prove and
+ *                   decider entries take it as it stands with SRS_SPACE_DEVICE.  After the advice upload everything stays on the
+ *                   device: l, t, m, h, g are written at their final offsets (one multiplicity pass and one h/g launch for all
+ *                   lookups), and only the commitments come back.
+ *   W_commitments   HOST, srs_structure_num_rounds points.   challenges_io: HOST, srs_structure_num_challenges elements of the
+ *                   curve's scalar field (Montgomery).
+ *   ro != NULL      the transcript of the reference: the oracle (over the curve's BASE field, else SRS_ERR_INVALID) absorbs the
+ *                   instances -- scalar-field elements, each converted as util::fe_to_fe does (src/util/mod.rs:87-89): the canonical
+ *                   integer reduced modulo the oracle field's modulus --, then after each round absorb_point(C_i) and
+ *                   squeeze::<C::ScalarExt>(128) (:478-489, :537-545, :562-564, :588-650).  _0 touches neither ro nor instances.
+ *   ro == NULL      with challenges: they are READ from challenges_io (the r_io convention of srs_sangria_prove).
+ * Every argument check comes before anything is written -- W_dev, W_commitments, challenges_io and ro are untouched on
+ * SRS_ERR_INVALID / _UNSUPPORTED / _TOO_LONG_INPUT (a round longer than the key, commitment::Error::TooLongInput).  Two of these
+ * checks DEVIATE from where the reference fails: a column longer than 2^k (the reference commits the longer vector) and, in a
+ * structure with lookups, a column shorter than 2^k (LookupEvalDomain reads the unpadded columns and fails on the missing row) are
+ * both refused up front with SRS_ERR_INVALID.  Keys sharded over processes and row-sharded structures are refused
+ * (SRS_ERR_INVALID: the challenges need the full commitments); a multi-device key is accepted.  After SRS_ERR_DEVICE W_dev and
+ * the oracle's state are lost.  The call ends synchronised with `stream`. */
+size_t srs_structure_num_rounds(const srs_structure *S);              /* round_sizes.len(): 1, 1, 2, 3 for _0 .. _3 */
+size_t srs_structure_round_len(const srs_structure *S, size_t round); /* round_sizes[round]; 0 past the last round */
+int srs_run_sps_protocol(srs_structure *S, srs_ck *ck, srs_poseidon *ro, const srs_fe *instances, size_t n_instances,
+                         const srs_fe *const *columns, const size_t *lens, size_t n_columns, int space,
+                         srs_fe *W_dev, void *stream, srs_fe *challenges_io, srs_affine *W_commitments);
+
 /* batch_invert_assigned (src/util/mod.rs:119-153) for ONE column of halo2 `Assigned<F>` cells flattened by the caller:
  *   Zero -> (0, no denominator), Trivial(x) -> (x, no denominator), Rational(n, d) -> (n, d)
  * out[i] = numerators[i] * (has_denominator[i] ? denominators[i]^-1 : 1), a zero denominator giving 0 (ff::BatchInvert skips

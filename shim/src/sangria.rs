@@ -41,6 +41,25 @@ pub fn commit_cross_terms<C: GpuCurve>(s: &GpuStructure, ck: &GpuKey<C>, w1: &[C
     Ok((terms, commits))
 }
 
+/// `PlonkStructure::run_sps_protocol` (src/plonk/mod.rs:413-428) as one call: `advice` = the columns `try_collect_witness` leaves behind,
+/// `instances` flattened, `ro` the `ro_nark` handle (null: the challenges are read from `challenges`).  `w` (num_witness_columns << k
+/// elements) receives `W[0] || W[1] (|| W[2])`, the vector `prove_incoming` and the deciders read.  -> (W_commitments, challenges);
+/// rc 1 maps to `SpsError::WrongCommitmentSize`, rc 10 to `UnsupportedChallengesCount`.
+pub fn run_sps_protocol<C: GpuCurve>(s: &GpuStructure, ck: &GpuKey<C>, ro: *mut srs_poseidon, instances: &[C::ScalarExt],
+                                      advice: &[Vec<C::ScalarExt>], w: &mut crate::commit::DeviceVec<C::ScalarExt>,
+                                      mut challenges: Vec<C::ScalarExt>) -> Result<(Vec<C>, Vec<C::ScalarExt>), ShimError> {
+    let cols: Vec<*const srs_fe> = advice.iter().map(|c| c.as_ptr() as *const srs_fe).collect();
+    let lens: Vec<usize> = advice.iter().map(|c| c.len()).collect();
+    let rounds = unsafe { srs_structure_num_rounds(s.raw) };
+    assert!(challenges.len() == unsafe { srs_structure_num_challenges(s.raw) });
+    assert!(w.len() >= (0..rounds).map(|i| unsafe { srs_structure_round_len(s.raw, i) }).sum::<usize>());
+    let mut commitments = vec![C::identity(); rounds];
+    check(unsafe { srs_run_sps_protocol(s.raw, ck.raw, ro, instances.as_ptr() as *const srs_fe, instances.len(), cols.as_ptr(), lens.as_ptr(),
+                                        cols.len(), SRS_SPACE_HOST, w.raw as *mut srs_fe, ptr::null_mut(), challenges.as_mut_ptr() as *mut srs_fe,
+                                        commitments.as_mut_ptr() as *mut srs_affine) })?;
+    Ok((commitments, challenges))
+}
+
 /// `RelaxedPlonkWitness::fold`, one round vector: out = w1 + r * w2
 pub fn fold_witness<F: Copy>(field: i32, out: &mut [F], w1: &[F], w2: &[F], r: &F) -> Result<(), ShimError> {
     assert!(out.len() == w1.len() && w1.len() == w2.len());

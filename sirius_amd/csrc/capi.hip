@@ -1113,16 +1113,35 @@ struct StreamRes {
     uint64_t *peer_bytes = nullptr;
 };
 
+// A tail of the committed vector that is COMPUTED on the device from the uploaded part (run_sps_protocol_2: ls | ts | ms behind the advice):
+// dst[n, n + len), filled by produce() -- which enqueues on the caller's stream, after every upload -- and accumulated as further sets
+// of the same commit (cut: piece boundaries relative to n; base offsets n + cut[t]).  Unsharded keys only.
+struct Tail {
+    std::vector<size_t> cut;
+    std::function<int()> produce;
+};
+// pieces of a tail of `len` elements: one set up to 2^22 elements, equal 1024-aligned pieces beyond
+std::vector<size_t> tail_cuts(size_t len) {
+    const size_t pieces = (len + ((size_t)1 << 22) - 1) >> 22, per = ((len + pieces - 1) / pieces + 1023) / 1024 * 1024;
+    std::vector<size_t> cut(1, 0);
+    for (size_t a = per; a < len; a += per) cut.push_back(a);
+    cut.push_back(len);
+    return cut;
+}
+
 // -> the commitment as an XYZZ point (the caller normalises: a multi-device key adds its shards' partial sums first)
 int commit_streamed_core(StreamRes ck_, const std::vector<Seg> &segs, size_t n, const std::vector<size_t> &cut, fe_t *dst, int repr,
-                         hipStream_t st, xyzz_t *sum_out) {
+                         hipStream_t st, xyzz_t *sum_out, const Tail *tail = nullptr) {
     StreamRes *ck = &ck_;
     HostTrace ht("commit_streamed");
-    const size_t chunks = cut.size() - 1;
+    const size_t chunks = cut.size() - 1, tails = tail ? tail->cut.size() - 1 : 0, sets = chunks + tails;
+    const size_t n_all = n + (tail ? tail->cut.back() : 0);
     const uint32_t W = ck->key.world;
     const Stripes sp{ck->key.rank, W};       // sp.count(a, b): this rank's elements of [a, b)
+    if (tail && (W != 1 || sets > msm::LANDING_SLOTS)) return fail(SRS_ERR_DEVICE, "internal: commit_streamed: tail on a sharded key / too many sets");
     size_t per = 0;
     for (size_t j = 0; j < chunks; ++j) per = std::max(per, sp.count(cut[j], cut[j + 1]));
+    for (size_t t = 0; t < tails; ++t) per = std::max(per, tail->cut[t + 1] - tail->cut[t]);
     if (!ck->copy_stream) SRS_HIP_CHECK(hipStreamCreateWithFlags(&ck->copy_stream, hipStreamNonBlocking));
     while (ck->events.size() < chunks + 1) {
         hipEvent_t e;
@@ -1132,10 +1151,12 @@ int commit_streamed_core(StreamRes ck_, const std::vector<Seg> &segs, size_t n, 
     // the copy stream must not overwrite dst while earlier work on the caller's stream still reads it
     SRS_HIP_CHECK(hipEventRecord(ck->events[chunks], st));
     SRS_HIP_CHECK(hipStreamWaitEvent(ck->copy_stream, ck->events[chunks], 0));
-    std::vector<bool> launched(chunks, false);
+    std::vector<bool> launched(sets, false);
     // every chunk on the 16-bit windows: the chunks fold their buckets into one running set and only the last one is reduced
-    bool fold = chunks > 1;
+    bool fold = sets > 1;
     for (size_t j = 0; j < chunks; ++j) fold = fold && sp.count(cut[j], cut[j + 1]) > 0;
+    for (size_t t = 0; t < tails; ++t) fold = fold && tail->cut[t + 1] > tail->cut[t];
+    auto fold_of = [&](size_t j) { return !fold ? msm::FOLD_NONE : (j == 0 ? msm::FOLD_FIRST : (j + 1 == sets ? msm::FOLD_LAST : msm::FOLD_MIDDLE)); };
     msm::reserve(ck->key, (uint32_t)per, 1);
     auto upload_chunk = [&](size_t j) {    // the rank's stripes of [cut_j, cut_j+1): copies per piece, memsets for the padding (world == 1: all of it)
         const size_t up = upload(dst, segs, cut[j], cut[j + 1], sp, ck->copy_stream);
@@ -1158,8 +1179,7 @@ int commit_streamed_core(StreamRes ck_, const std::vector<Seg> &segs, size_t n, 
             return;
         }
         SRS_HIP_CHECK(hipStreamWaitEvent(st, ck->events[j], 0));
-        const msm::Fold f = !fold ? msm::FOLD_NONE : (j == 0 ? msm::FOLD_FIRST : (j + 1 == chunks ? msm::FOLD_LAST : msm::FOLD_MIDDLE));
-        launched[j] = msm::enqueue(ck->key, &ptr, &nn, &base, 1, repr == SRS_REPR_MONT, st, (uint32_t)j, f);
+        launched[j] = msm::enqueue(ck->key, &ptr, &nn, &base, 1, repr == SRS_REPR_MONT, st, (uint32_t)j, fold_of(j));
     };
     // Page-locked source: the uploads are asynchronous -- upload j + 1 is queued before the launches of MSM j, the copy engine never waits
     // for the host.  PAGEABLE source (a Rust Vec<F>: the runtime stages it through its own pinned buffers and hipMemcpyAsync returns only
@@ -1177,6 +1197,18 @@ int commit_streamed_core(StreamRes ck_, const std::vector<Seg> &segs, size_t n, 
             launch(j);
         }
     }
+    if (tail) {                              // the caller's stream has waited for every upload: the tail is computed, then accumulated
+        int prc = tail->produce();
+        if (prc) {
+            (void)hipStreamSynchronize(st);      // the sets already enqueued use the key's scratch
+            return prc;
+        }
+        for (size_t t = 0; t < tails; ++t) {
+            const fe_t *ptr = dst + n + tail->cut[t];
+            const uint32_t nn = (uint32_t)(tail->cut[t + 1] - tail->cut[t]), base = (uint32_t)(n + tail->cut[t]);
+            if (nn) launched[chunks + t] = msm::enqueue(ck->key, &ptr, &nn, &base, 1, repr == SRS_REPR_MONT, st, (uint32_t)(chunks + t), fold_of(chunks + t));
+        }
+    }
     ht.mark("enqueued");
     SRS_HIP_CHECK(hipStreamSynchronize(st));
     SRS_HIP_CHECK(hipGetLastError());
@@ -1185,24 +1217,24 @@ int commit_streamed_core(StreamRes ck_, const std::vector<Seg> &segs, size_t n, 
     // vector is in HBM by now, so the commit is simply run again, device-resident, with the prediction switched
     bool missed = false;
     std::vector<uint32_t> used_slots;
-    for (size_t j = 0; j < chunks; ++j) {
+    for (size_t j = 0; j < sets; ++j) {
         if (!launched[j]) continue;
         used_slots.push_back((uint32_t)j);
         missed = missed || msm::overflow_missed(ck->key, (uint32_t)j);
     }
-    msm::note_commit(ck->key, used_slots.data(), (uint32_t)used_slots.size(), sp.count(0, n));   // + the scalars: the density the next commit's cuts follow
+    msm::note_commit(ck->key, used_slots.data(), (uint32_t)used_slots.size(), sp.count(0, n_all));   // + the scalars: the density the next commit's cuts follow
     xyzz_t redo;
     if (missed) {
         ++ck->key.stat_redo;
         const fe_t *whole = dst;
-        const uint32_t n_local = (uint32_t)sp.count(0, n);
+        const uint32_t n_local = (uint32_t)sp.count(0, n_all);
         msm::run(ck->key, &whole, &n_local, 1, repr == SRS_REPR_MONT, st, &redo);
         ht.mark("overflow redo");
     }
     auto go = [&](auto tag) {
         using C = decltype(tag);
         xyzz_t acc = Ec<C>::identity(), part;
-        for (size_t j = fold ? chunks - 1 : 0; j < chunks && !missed; ++j) {          // folded chunks: the last set holds the whole sum
+        for (size_t j = fold ? sets - 1 : 0; j < sets && !missed; ++j) {          // folded chunks: the last set holds the whole sum
             msm::finish(ck->key, 1, (uint32_t)j, launched[j], &part);
             acc = Ec<C>::add(acc, part);
         }
@@ -1218,10 +1250,10 @@ int commit_streamed_core(StreamRes ck_, const std::vector<Seg> &segs, size_t n, 
 
 // single-device (or process-sharded) key handle: the commit on the handle's own resources, normalised
 int commit_streamed(srs_ck *ck, const std::vector<Seg> &segs, size_t n, const std::vector<size_t> &cut, fe_t *dst, int repr,
-                    hipStream_t st, srs_affine *out) {
+                    hipStream_t st, srs_affine *out, const Tail *tail = nullptr) {
     xyzz_t sum;
     StreamRes r{ck->key, ck->copy_stream, ck->events};
-    int rc = commit_streamed_core(r, segs, n, cut, dst, repr, st, &sum);
+    int rc = commit_streamed_core(r, segs, n, cut, dst, repr, st, &sum, tail);
     if (rc) return rc;
     store_affine(ck->key.curve, &sum, 1, out);
     return SRS_OK;
@@ -2228,6 +2260,151 @@ int srs_is_sat_log_derivative(srs_structure *S, const srs_fe *W, int space, void
         const fe_t *dW = nullptr;
         z.place([&] { dW = z.in(reinterpret_cast<const fe_t *>(W), wlen); });
         *mismatch_count = rowprog::log_derivative_mismatches(s, dW, st);      // ends synchronised
+        return SRS_OK;
+    });
+}
+
+// ------------------------------------------------------------------ trace generation
+size_t srs_structure_num_rounds(const srs_structure *S) {
+    if (!S) return 0;
+    return rowprog::num_lookups(S->s) ? (rowprog::has_vector_lookup(S->s) ? 3 : 2) : 1;
+}
+size_t srs_structure_round_len(const srs_structure *S, size_t round) {      // ConstraintSystemMetainfo::round_sizes
+    if (!S || round >= srs_structure_num_rounds(S)) return 0;
+    const size_t rows = rowprog::rows(S->s), na = rowprog::num_advice(S->s), L = rowprog::num_lookups(S->s);
+    if (!L) return na * rows;
+    if (rowprog::has_vector_lookup(S->s)) return (round == 0 ? na : (round == 1 ? 3 * L : 2 * L)) * rows;
+    return (round == 0 ? na + 3 * L : 2 * L) * rows;
+}
+
+// util::fe_to_fe (src/util/mod.rs:87-89): the canonical integer of an element of field `from`, reduced modulo the modulus of field `to`
+// (both moduli lie between 2^253 and 2^254: one subtraction reduces)
+static fe_t fe_to_fe(int from, int to, const fe_t &x) {
+    const fe_t c = from == SRS_FIELD_FR ? Fr::from_mont(x) : Fq::from_mont(x);
+    return to == SRS_FIELD_FR ? Fr::to_mont(Fr::reduce_once(c)) : Fq::to_mont(Fq::reduce_once(c));
+}
+
+// PlonkStructure::run_sps_protocol (src/plonk/mod.rs:413-662).  Every check comes before anything is written; the outputs in host
+// memory (commitments, challenges) are written once, at the end.
+int srs_run_sps_protocol(srs_structure *S, srs_ck *ck, srs_poseidon *ro, const srs_fe *instances, size_t n_instances,
+                         const srs_fe *const *columns, const size_t *lens, size_t n_columns, int space, srs_fe *W_dev, void *stream,
+                         srs_fe *challenges_io, srs_affine *W_commitments) {
+    if (!S || !ck || !W_dev || !W_commitments || (n_columns && (!columns || !lens)) || (n_instances && !instances))
+        return fail(SRS_ERR_INVALID, "srs_run_sps_protocol: bad argument");
+    rowprog::Structure *s = S->s;
+    const size_t nch = rowprog::num_challenges(s), L = rowprog::num_lookups(s), na = rowprog::num_advice(s), rows = rowprog::rows(s);
+    const size_t n_rounds = srs_structure_num_rounds(S);
+    const bool vector = rowprog::has_vector_lookup(s);
+    if (nch > 3)      // :426
+        return fail(SRS_ERR_UNSUPPORTED, "srs_run_sps_protocol: UnsupportedChallengesCount { challenges_count: " + std::to_string(nch) + " }");
+    if ((nch >= 2) != (L > 0) || (nch == 3) != vector)      // _2 / _3 without lookup arguments: SpsError::LackOfLookupArguments
+        return fail(SRS_ERR_INVALID, "srs_run_sps_protocol: " + std::to_string(nch) + " challenges do not fit the structure's lookup arguments");
+    if (nch && !challenges_io) return fail(SRS_ERR_INVALID, "srs_run_sps_protocol: bad argument");
+    const int curve = ck->key.curve, sf = srs_scalar_field_of(curve), bf = curve == SRS_CURVE_BN256 ? SRS_FIELD_FQ : SRS_FIELD_FR;
+    if (rowprog::field(s) != sf) return fail(SRS_ERR_INVALID, "srs_run_sps_protocol: the structure's field is not the key's scalar field");
+    if (ro && nch && ro->h->field != bf)
+        return fail(SRS_ERR_INVALID, "srs_run_sps_protocol: the oracle's field is not the curve's base field");
+    if (rowprog::shard_world(s) > 1 || (ck->shards.empty() && ck->key.world > 1))      // the challenges need the full commitments
+        return fail(SRS_ERR_INVALID, "srs_run_sps_protocol: structure / key is sharded over processes; use the step-wise calls and add the ranks' partial commitments");
+    if (n_columns != na)
+        return fail(SRS_ERR_INVALID, "srs_run_sps_protocol: " + std::to_string(n_columns) + " columns for " + std::to_string(na) + " advice columns");
+    for (size_t c = 0; c < n_columns; ++c) {
+        if (lens[c] > rows) return fail(SRS_ERR_INVALID, "srs_run_sps_protocol: advice column " + std::to_string(c) + " is longer than 2^k");
+        if (L && lens[c] != rows)      // LookupEvalDomain reads the unpadded columns
+            return fail(SRS_ERR_INVALID, "srs_run_sps_protocol: advice column " + std::to_string(c) + " is shorter than 2^k in a structure with lookups");
+        if (lens[c] && !columns[c]) return fail(SRS_ERR_INVALID, "srs_run_sps_protocol: null column");
+    }
+    for (size_t i = 0; i < n_rounds; ++i)
+        if (srs_structure_round_len(S, i) > ck->key.global_len) return too_long_input(srs_structure_round_len(S, i), ck);
+    int rc = ensure_device();
+    if (rc) return rc;
+    std::lock_guard<std::recursive_mutex> key_lock(ck->mu);
+    return guarded([&]() -> int {
+        HostTrace ht("srs_run_sps_protocol");
+        hipStream_t st = (hipStream_t)stream;
+        fe_t *W = reinterpret_cast<fe_t *>(W_dev);
+        std::vector<srs_affine> cm(n_rounds);
+        std::vector<fe_t> ch(nch ? nch : 1);
+        std::string err;
+        if (!ro && nch) std::memcpy(ch.data(), challenges_io, nch * sizeof(fe_t));
+        if (ro && nch && n_instances) {      // [pi.instance]: first in every variant's transcript
+            std::vector<fe_t> conv(n_instances);
+            for (size_t i = 0; i < n_instances; ++i) conv[i] = fe_to_fe(sf, bf, reinterpret_cast<const fe_t *>(instances)[i]);
+            poseidon::absorb(*ro->h, conv.data(), n_instances);
+        }
+        // [C_i] -> ]r_i[ ; without an oracle r_i is the caller's
+        auto challenge = [&](size_t i) -> int {
+            if (!ro || i >= nch) return SRS_OK;
+            poseidon::absorb(*ro->h, reinterpret_cast<const fe_t *>(&cm[i]), 2);
+            if (!poseidon::squeeze(*ro->h, 128, sf, ch[i], err)) return fail(SRS_ERR_INVALID, "srs_run_sps_protocol: " + err);
+            return SRS_OK;
+        };
+        auto commit_round = [&](size_t i, size_t off) -> int {      // a round that lies in W_dev
+            return srs_commit(ck, reinterpret_cast<const srs_fe *>(W + off), srs_structure_round_len(S, i), SRS_SPACE_DEVICE, SRS_REPR_MONT, stream, &cm[i]);
+        };
+        // ---- round 0: the advice, padded (concatenate_with_padding), under one commitment with (ls, ts, ms) in _2
+        const bool advice_only = !L || vector;
+        const std::vector<size_t> adv_cut = commit_cuts(na * rows, std::max<size_t>(rows, 1024), 0, key_density(ck->key));      // as srs_commit_upload_columns cuts full columns
+        int crc;
+        if (space != SRS_SPACE_DEVICE && advice_only) {
+            crc = srs_commit_upload_columns(ck, columns, lens, n_columns, rows, W_dev, SRS_REPR_MONT, stream, &cm[0]);
+        } else if (space != SRS_SPACE_DEVICE && ck->shards.empty() && adv_cut.size() > 2 &&
+                   adv_cut.size() + tail_cuts(3 * L * rows).size() - 2 <= msm::LANDING_SLOTS) {
+            // _2 from host columns on a single-device key, advice long enough to be cut into chunks: it streams up as in
+            // srs_commit_upload_columns (commit_streamed: chunk j + 1 goes up while chunk j is accumulated); once it is all there,
+            // (ls, ts, ms) are computed behind it with r = 0 (:516) and join the SAME commit as further sets at base offset
+            // num_advice * 2^k.  (Advice of ONE chunk has no upload to overlap: two sets would only pay the chunked commit's slot
+            // reduction where a whole MSM does not -- it takes the branch below.)
+            std::vector<Seg> segs;
+            for (size_t c = 0; c < n_columns; ++c) segs.push_back(Seg{reinterpret_cast<const fe_t *>(columns[c]), c * rows, lens[c]});
+            Tail tail;
+            tail.cut = tail_cuts(3 * L * rows);
+            tail.produce = [&]() -> int {
+                int erc = rowprog::sps_lookup_round_1(s, W, Fr::zero(), st, err);
+                return erc ? fail(erc, "srs_run_sps_protocol: " + err) : SRS_OK;
+            };
+            crc = commit_streamed(ck, segs, na * rows, adv_cut, W, SRS_REPR_MONT, st, &cm[0], &tail);
+        } else {
+            if (space != SRS_SPACE_DEVICE) {      // short advice, multi-device key: the advice goes up first, the whole round is committed from HBM
+                std::vector<Seg> segs;
+                for (size_t c = 0; c < n_columns; ++c) segs.push_back(Seg{reinterpret_cast<const fe_t *>(columns[c]), c * rows, lens[c]});
+                upload(W, segs, 0, na * rows, Stripes{0, 1}, st);
+            } else {
+                for (size_t c = 0; c < n_columns; ++c) {      // a column that already lies at its place stays
+                    fe_t *dst = W + c * rows;
+                    if (lens[c] && reinterpret_cast<const fe_t *>(columns[c]) != dst)
+                        SRS_HIP_CHECK(hipMemcpyAsync(dst, columns[c], lens[c] * sizeof(fe_t), hipMemcpyDeviceToDevice, st));
+                    if (lens[c] < rows) SRS_HIP_CHECK(hipMemsetAsync(dst + lens[c], 0, (rows - lens[c]) * sizeof(fe_t), st));
+                }
+            }
+            if (!advice_only) {      // _2: evaluate_coefficient_1 with r = 0 (:516)
+                int erc = rowprog::sps_lookup_round_1(s, W, Fr::zero(), st, err);
+                if (erc) return fail(erc, "srs_run_sps_protocol: " + err);
+            }
+            crc = commit_round(0, 0);
+        }
+        if (crc) return crc;
+        if ((crc = challenge(0))) return crc;
+        ht.mark("round 0");
+        // ---- the lookup rounds, written in place behind the advice
+        if (L) {
+            size_t round = 1;
+            if (vector) {      // _3: evaluate_coefficient_1 with r1 (:614)
+                int erc = rowprog::sps_lookup_round_1(s, W, ch[0], st, err);
+                if (erc) return fail(erc, "srs_run_sps_protocol: " + err);
+                if ((crc = commit_round(1, na * rows))) return crc;
+                if ((crc = challenge(1))) return crc;
+                round = 2;
+            }
+            rowprog::sps_lookup_round_2(s, W, ch[round - 1], st);      // evaluate_coefficient_2 (:548, :634)
+            if ((crc = commit_round(round, (na + 3 * L) * rows))) return crc;
+            if ((crc = challenge(round))) return crc;
+            ht.mark("lookup rounds");
+        }
+        SRS_HIP_CHECK(hipGetLastError());
+        prof::collect();
+        std::memcpy(W_commitments, cm.data(), n_rounds * sizeof(srs_affine));
+        if (nch) std::memcpy(challenges_io, ch.data(), nch * sizeof(fe_t));
         return SRS_OK;
     });
 }

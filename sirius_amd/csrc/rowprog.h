@@ -31,6 +31,7 @@ size_t num_challenges(const Structure *S);    // PlonkStructure::num_challenges
 size_t num_advice(const Structure *S);
 size_t num_witness_columns(const Structure *S);   // num_advice + 5 * num_lookups: columns of W[0] || W[1] || ...
 size_t num_lookups(const Structure *S);
+bool has_vector_lookup(const Structure *S);
 size_t rows(const Structure *S);
 int field(const Structure *S);
 
@@ -101,6 +102,9 @@ bool jit_selfcheck(size_t *code_bytes, std::string &log);
 int lookup_coeff_1(Structure *S, const fe_t *advice_dev, const fe_t &r, fe_t *const *ls, fe_t *const *ts, fe_t *const *ms,
                    hipStream_t st, std::string &err);
 void lookup_coeff_2(int field, const fe_t *l, const fe_t *t, const fe_t *m, const fe_t &r, size_t n, fe_t *h, fe_t *g, hipStream_t st);
+// run_sps_protocol's lookup rounds in place on W_dev = advice | ls | ts | ms | hs | gs (groups of num_lookups columns): enqueue only
+int sps_lookup_round_1(Structure *S, fe_t *W_dev, const fe_t &r, hipStream_t st, std::string &err);      // advice -> ls, ts, ms
+void sps_lookup_round_2(Structure *S, fe_t *W_dev, const fe_t &r, hipStream_t st);                       // ls, ts, ms -> hs, gs
 size_t log_derivative_mismatches(Structure *S, const fe_t *W_dev, hipStream_t st);
 // batch_invert_assigned (src/util/mod.rs:119-153); has_den may be nullptr (every element has a denominator)
 void assigned_invert(int field, const fe_t *num, const fe_t *den, const uint8_t *has_den, size_t n, fe_t *out, hipStream_t st);

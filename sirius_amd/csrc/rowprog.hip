@@ -583,7 +583,10 @@ __global__ void k_count_mismatch(const fe_t *__restrict__ a, const fe_t *__restr
 // open-addressing table (slot = row index of the smallest row with that value, resolved with atomicMin so the
 // result does not depend on scheduling), l is counted into the slots, and every row of t reads its slot back.
 // Values compare by their Montgomery limbs (a bijection of the canonical form `to_repr` the reference hashes).
-constexpr uint32_t M_EMPTY = 0xFFFFFFFFu;
+// A slot holds row + 1, 0 = empty: ONE clear zeroes the rows and the counts of every table together.
+// blockIdx.y = the lookup: its columns lie y * n elements, its tables y * (mask + 1) slots behind the pointers (run_sps_protocol's
+// witness layout, sps_lookup_round_1); a launch for one lookup has gridDim.y = 1.
+constexpr uint32_t M_EMPTY = 0u;
 __device__ __forceinline__ uint32_t fe_hash(const fe_t &x) {
     uint32_t h = 0x9E3779B9u;
 #pragma unroll
@@ -597,12 +600,14 @@ __device__ __forceinline__ uint32_t fe_hash(const fe_t &x) {
 __global__ void k_m_insert(const fe_t *__restrict__ t, uint32_t n, uint32_t *__restrict__ slot_row, uint32_t mask) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    t += (size_t)blockIdx.y * n;
+    slot_row += (size_t)blockIdx.y * ((size_t)mask + 1);
     const fe_t key = t[i];
     uint32_t s = fe_hash(key) & mask;
     for (;;) {
-        uint32_t cur = atomicCAS(&slot_row[s], M_EMPTY, i);
+        uint32_t cur = atomicCAS(&slot_row[s], M_EMPTY, i + 1);
         if (cur == M_EMPTY) return;
-        if (Fr::eq(t[cur], key)) { atomicMin(&slot_row[s], i); return; }
+        if (Fr::eq(t[cur - 1], key)) { atomicMin(&slot_row[s], i + 1); return; }
         s = (s + 1) & mask;
     }
 }
@@ -610,12 +615,16 @@ __global__ void k_m_count(const fe_t *__restrict__ l, uint32_t n, const fe_t *__
                           uint32_t *__restrict__ slot_cnt, uint32_t mask) {
     uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= n) return;
+    l += (size_t)blockIdx.y * n;
+    t += (size_t)blockIdx.y * n;
+    slot_row += (size_t)blockIdx.y * ((size_t)mask + 1);
+    slot_cnt += (size_t)blockIdx.y * ((size_t)mask + 1);
     const fe_t key = l[j];
     uint32_t s = fe_hash(key) & mask;
     for (;;) {
         uint32_t cur = slot_row[s];
         if (cur == M_EMPTY) return;                       // value not in the table
-        if (Fr::eq(t[cur], key)) { atomicAdd(&slot_cnt[s], 1u); return; }
+        if (Fr::eq(t[cur - 1], key)) { atomicAdd(&slot_cnt[s], 1u); return; }
         s = (s + 1) & mask;
     }
 }
@@ -624,28 +633,35 @@ __global__ void k_m_emit(const fe_t *__restrict__ t, uint32_t n, const uint32_t 
                          const uint32_t *__restrict__ slot_cnt, uint32_t mask, fe_t *__restrict__ m) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    t += (size_t)blockIdx.y * n;
+    m += (size_t)blockIdx.y * n;
+    slot_row += (size_t)blockIdx.y * ((size_t)mask + 1);
+    slot_cnt += (size_t)blockIdx.y * ((size_t)mask + 1);
     const fe_t key = t[i];
     uint32_t s = fe_hash(key) & mask;
     for (;;) {
         uint32_t cur = slot_row[s];
-        if (cur == i || Fr::eq(t[cur], key)) break;     // every row of t was inserted: the probe terminates
+        if (cur == i + 1 || Fr::eq(t[cur - 1], key)) break;     // every row of t was inserted: the probe terminates, on a filled slot
         s = (s + 1) & mask;
     }
-    uint32_t c = slot_row[s] == i ? slot_cnt[s] : 0u;
+    uint32_t c = slot_row[s] == i + 1 ? slot_cnt[s] : 0u;
     m[i] = c ? F::from_u64(c) : F::zero();               // F::from_u128(count), lookup.rs:295-300
 }
 
 // evaluate_h_g (lookup.rs:305-317): h = 1 / (l + r), g = m / (t + r), with 1/0 := 0.
 // One field inversion per HG_CHUNK elements (Montgomery's trick); elements of a chunk are blockDim apart, so
-// every load / store is coalesced.  blockIdx.y: 0 -> h, 1 -> g.
+// every load / store is coalesced.  blockIdx.y: 0 -> h, 1 -> g.  blockIdx.z = the lookup: its five columns lie z * n elements behind
+// the pointers (sps_lookup_round_2); a launch for one lookup has gridDim.z = 1.
 constexpr uint32_t HG_THREADS = 128, HG_CHUNK = 8;
 template <class F>
 __global__ void SRS_KERNEL_BOUNDS(HG_THREADS, 1)
 k_lookup_hg(const fe_t *__restrict__ l, const fe_t *__restrict__ t, const fe_t *__restrict__ m, fe_t r, uint32_t n,
             fe_t *__restrict__ h, fe_t *__restrict__ g) {
     const bool is_g = blockIdx.y == 1;
-    const fe_t *__restrict__ src = is_g ? t : l;
-    fe_t *__restrict__ dst = is_g ? g : h;
+    const size_t col = (size_t)blockIdx.z * n;
+    const fe_t *__restrict__ src = (is_g ? t : l) + col;
+    fe_t *__restrict__ dst = (is_g ? g : h) + col;
+    m += col;
     const uint32_t base = blockIdx.x * HG_THREADS * HG_CHUNK + threadIdx.x;
     fe_t v[HG_CHUNK], pref[HG_CHUNK];
     uint32_t zero_mask = 0;
@@ -856,6 +872,7 @@ struct Structure : Compiled {     // Compiled (rowprog_compile.h): the programs,
     fe_t *d_vinv = nullptr, *d_vinv29 = nullptr;
     fe_t *d_kM[2] = {nullptr, nullptr};      // pg_K_from_G_device: the full inverse Vandermonde matrix of the nodes 0..d_G / 1..d_G+1 (made on first use)
     Arena arena;
+    Arena lookup_scratch;              // sps_lookup_round_1: the multiplicity tables of every lookup (grow-only)
     std::vector<uint8_t> host_stage;   // source of the per-call staging copy (must outlive the asynchronous copy)
     uint32_t shard_rank = 0, shard_world = 1;   // cross terms: evaluate only this rank's row stripes (set_shard)
 };
@@ -957,6 +974,7 @@ void destroy(Structure *S) {
     jit::release(S->cross.jit);
     for (void *p : S->owned) (void)hipFree(p);
     S->arena.release();
+    S->lookup_scratch.release();
     delete S;
 }
 
@@ -973,6 +991,7 @@ size_t num_challenges(const Structure *S) { return S->s_num_challenges; }
 size_t num_advice(const Structure *S) { return S->num_advice; }
 size_t num_witness_columns(const Structure *S) { return S->num_advice + 5 * S->num_lookups; }
 size_t num_lookups(const Structure *S) { return S->num_lookups; }
+bool has_vector_lookup(const Structure *S) { return S->has_vector_lookup; }
 size_t rows(const Structure *S) { return S->rows; }
 size_t num_gates(const Structure *S) { return S->gate_progs.size(); }
 int field(const Structure *S) { return S->field; }
@@ -1971,8 +1990,7 @@ int lookup_coeff_1(Structure *S, const fe_t *advice_dev, const fe_t &r, fe_t *co
         const uint32_t blocks = (n + 255) / 256;
         for (size_t i = 0; i < L; ++i) {
             prof::Scope ps("lookup_m", st, n);
-            SRS_HIP_CHECK(hipMemsetAsync(d_row, 0xFF, (size_t)cap * sizeof(uint32_t), st));
-            SRS_HIP_CHECK(hipMemsetAsync(d_cnt, 0, (size_t)cap * sizeof(uint32_t), st));
+            SRS_HIP_CHECK(hipMemsetAsync(d_row, 0, (size_t)cap * 2 * sizeof(uint32_t), st));      // rows (M_EMPTY) and counts
             SRS_LAUNCH(k_m_insert, (blocks), (256), 0, st, (const fe_t *)ts[i], n, d_row, cap - 1);
             SRS_LAUNCH(k_m_count, (blocks), (256), 0, st, (const fe_t *)ls[i], n, (const fe_t *)ts[i], (const uint32_t *)d_row, d_cnt, cap - 1);
             if (S->field == 0) SRS_LAUNCH((k_m_emit<Fr>), (blocks), (256), 0, st, (const fe_t *)ts[i], n, (const uint32_t *)d_row, (const uint32_t *)d_cnt, cap - 1, ms[i]);
@@ -1984,6 +2002,50 @@ int lookup_coeff_1(Structure *S, const fe_t *advice_dev, const fe_t &r, fe_t *co
     (void)hipFree(d_row);
     prof::collect();
     return 0;
+}
+
+// run_sps_protocol_2 / _3 (src/plonk/mod.rs:503-662) on the witness IN PLACE: W_dev = advice | ls | ts | ms | hs | gs, every group
+// num_lookups columns of `rows` elements (the reference's concat_vec! grouping).  Both rounds only enqueue on `st` -- no allocation and
+// no synchronisation once the structure's scratch has grown to its size; the caller's commit of the round is what waits.
+// Round 1, evaluate_coefficient_1 (lookup.rs:319-341): the 2 L lookup / table programs write l_i, t_i to their places, then ONE
+// multiplicity pass for all lookups -- one clear, three launches with the lookup in blockIdx.y -- writes m_i.
+int sps_lookup_round_1(Structure *S, fe_t *W_dev, const fe_t &r, hipStream_t st, std::string &err) {
+    const size_t L = S->num_lookups;
+    if (!L) { err = "structure has no lookup arguments"; return 4; }    // SpsError::LackOfLookupArguments
+    if (L > 65535) { err = "more than 65535 lookup arguments"; return 4; }      // gridDim.y / .z
+    const uint32_t n = (uint32_t)S->rows;
+    fe_t *ls = W_dev + S->num_advice * S->rows, *ts = ls + L * S->rows, *ms = ts + L * S->rows;
+    for (size_t i = 0; i < 2 * L; ++i) {
+        fe_t *outs[1] = {ls + i * S->rows};
+        int rc = evaluate_prog(S, S->lookup_progs[i], 1, W_dev, nullptr, &r, 1, outs, st, err, false);
+        if (rc) return rc;
+    }
+    uint32_t cap = 2;
+    while (cap < 2 * n) cap <<= 1;
+    const size_t words = 2 * L * (size_t)cap;                 // [L][cap] rows, then [L][cap] counts
+    S->lookup_scratch.reserve(Arena::pad(words * sizeof(uint32_t)));
+    S->lookup_scratch.reset();
+    uint32_t *d_row = S->lookup_scratch.take<uint32_t>(words), *d_cnt = d_row + L * (size_t)cap;
+    const uint32_t blocks = (n + 255) / 256, gy = (uint32_t)L;
+    prof::Scope ps("lookup_m", st, n * L);
+    SRS_HIP_CHECK(hipMemsetAsync(d_row, 0, words * sizeof(uint32_t), st));
+    SRS_LAUNCH(k_m_insert, (blocks, gy), (256), 0, st, (const fe_t *)ts, n, d_row, cap - 1);
+    SRS_LAUNCH(k_m_count, (blocks, gy), (256), 0, st, (const fe_t *)ls, n, (const fe_t *)ts, (const uint32_t *)d_row, d_cnt, cap - 1);
+    if (S->field == 0) SRS_LAUNCH((k_m_emit<Fr>), (blocks, gy), (256), 0, st, (const fe_t *)ts, n, (const uint32_t *)d_row, (const uint32_t *)d_cnt, cap - 1, ms);
+    else SRS_LAUNCH((k_m_emit<Fq>), (blocks, gy), (256), 0, st, (const fe_t *)ts, n, (const uint32_t *)d_row, (const uint32_t *)d_cnt, cap - 1, ms);
+    return 0;
+}
+
+// Round 2, evaluate_coefficient_2 (lookup.rs:350-365): ONE launch reads l, t, m of every lookup from their places and writes h, g to theirs
+void sps_lookup_round_2(Structure *S, fe_t *W_dev, const fe_t &r, hipStream_t st) {
+    const size_t L = S->num_lookups, n = S->rows;
+    if (!L) return;
+    const fe_t *l = W_dev + S->num_advice * n, *t = l + L * n, *m = t + L * n;
+    fe_t *h = W_dev + (S->num_advice + 3 * L) * n, *g = h + L * n;
+    prof::Scope ps("lookup_hg", st, n * L);
+    const uint32_t gx = (uint32_t)((n + HG_THREADS * HG_CHUNK - 1) / (HG_THREADS * HG_CHUNK));
+    if (S->field == 0) SRS_LAUNCH((k_lookup_hg<Fr>), (gx, 2, (uint32_t)L), (HG_THREADS), 0, st, l, t, m, r, (uint32_t)n, h, g);
+    else SRS_LAUNCH((k_lookup_hg<Fq>), (gx, 2, (uint32_t)L), (HG_THREADS), 0, st, l, t, m, r, (uint32_t)n, h, g);
 }
 
 // Arguments::evaluate_h_g (lookup.rs:305-317) for one lookup: h = 1/(l + r), g = m/(t + r)

@@ -104,6 +104,47 @@ class PlonkStructure:
         except Exception:
             pass
 
+    @property
+    def num_rounds(self):
+        """round_sizes.len() (srs_structure_num_rounds): 1, 1, 2, 3 for run_sps_protocol_0 .. _3."""
+        return L.lib().srs_structure_num_rounds(self._h)
+
+    def round_len(self, i):
+        """round_sizes[i] (srs_structure_round_len)."""
+        return L.lib().srs_structure_round_len(self._h, i)
+
+    def run_sps_protocol(self, ck, instances, advice_cols, ro=None, challenges=None, W=None):
+        """`PlonkStructure::run_sps_protocol` (src/plonk/mod.rs:413-428) as one library call (srs_run_sps_protocol).
+        instances: the instance columns flattened (scalar-field elements); advice_cols: the advice columns, all numpy (host) or all
+        device tensors, each of at most 2^k elements (zero-padded; exactly 2^k with lookups).  ro: a PoseidonHash over the curve's
+        base field -- the challenges are squeezed from it as the reference does; with ro=None they are taken from `challenges`.
+        W: the device vector of num_witness_columns * 2^k elements to fill (allocated on the current device when None).
+        -> dict(W=<device vector, rounds concatenated>, rounds=[views per round], W_commitments=(rounds, 8), challenges=(n, 4))."""
+        bufs = [_buf(c, 4) for c in advice_cols]
+        space = bufs[0][1] if bufs else L.SPACE_HOST
+        assert all(b[1] == space for b in bufs)
+        ptrs = (C.c_void_p * max(len(bufs), 1))(*[b[0] for b in bufs])
+        lens = (C.c_size_t * max(len(bufs), 1))(*[b[2] for b in bufs])
+        inst = np.ascontiguousarray(instances if instances is not None else np.zeros((0, 4)), dtype=np.uint64).reshape(-1, 4)
+        n = self.num_witness_columns * self.rows
+        if W is None:
+            import torch
+            W = torch.empty((n, 4), dtype=torch.int64, device="cuda")
+        waddr, wspace, wn, keep_w = _buf(W, 4)
+        assert wspace == L.SPACE_DEVICE and wn == n
+        nch, nr = self.num_challenges, self.num_rounds
+        ch = np.zeros((nch, 4), dtype=np.uint64)
+        if ro is None and nch:
+            ch[:] = np.ascontiguousarray(challenges, dtype=np.uint64).reshape(nch, 4)
+        cm = np.zeros((nr, 8), dtype=np.uint64)
+        L.check(L.lib().srs_run_sps_protocol(self._h, ck._h, None if ro is None else ro._h, inst.ctypes.data, inst.shape[0], ptrs, lens,
+                                             len(bufs), space, waddr, _stream(), ch.ctypes.data, cm.ctypes.data))
+        rounds, off = [], 0
+        for i in range(nr):
+            rounds.append(W[off:off + self.round_len(i)])
+            off += self.round_len(i)
+        return dict(W=W, rounds=rounds, W_commitments=cm, challenges=ch)
+
     def eval_gates(self, W, challenges, homogeneous=False):
         """Per-row gate value; homogeneous=False: compressed gate, challenges = U.challenges;
         homogeneous=True: challenges = U.challenges || U.u."""
