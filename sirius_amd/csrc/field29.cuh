@@ -21,10 +21,31 @@
 #pragma once
 #include "field.cuh"
 
+// The emulator's audit build (tests/emu/field29_audit.h, -DSRS_EMU -DSRS_F29_AUDIT) gives f29_t a shadow -- the bounds its producer
+// declares -- and makes every operation below check its stated precondition on the operands' shadows.  Everywhere else the three
+// macros are empty: the product and the default emulator library compile the text they always did.
+#if defined(SRS_EMU) && defined(SRS_F29_AUDIT)
+#include "field29_audit.h"
+#define SRS_F29_SHADOW f29_audit::Shadow sh;
+#define SRS_F29_SITE , int site_line = __builtin_LINE(), const char *site_file = __builtin_FILE()
+#define SRS_F29_SITE_PASS , site_line, site_file
+#define SRS_F29_CHECK(...) f29_audit::Ops<Fp29, P>::__VA_ARGS__
+#define SRS_F29_LDS_LOAD(x, addr) (x).sh = f29_audit::lds_shadows()[addr]       // a word nobody stored comes back untracked
+#define SRS_F29_LDS_STORE(addr, x) f29_audit::lds_shadows()[addr] = (x).sh
+#else
+#define SRS_F29_SHADOW
+#define SRS_F29_SITE
+#define SRS_F29_SITE_PASS
+#define SRS_F29_CHECK(...)
+#define SRS_F29_LDS_LOAD(x, addr)
+#define SRS_F29_LDS_STORE(addr, x)
+#endif
+
 namespace srs {
 
 struct f29_t {
     uint32_t v[9];
+    SRS_F29_SHADOW
 };
 
 template <class P>
@@ -63,6 +84,7 @@ struct Fp29 {
         f29_t o;
 #pragma unroll
         for (int i = 0; i < 9; ++i) o.v[i] = 0;
+        SRS_F29_CHECK(zero(o));
         return o;
     }
     SRS_HD static bool is_zero_exact(const f29_t &a) {
@@ -92,10 +114,12 @@ struct Fp29 {
             if (sh > 3 && wi + 1 < 8) lo |= a.v[wi + 1] << (32 - sh);      // the limb straddles two words
             o.v[i] = i < 8 ? (lo & MASK) : lo;
         }
+        SRS_F29_CHECK(unpack(o));
         return o;
     }
     // normalised 9 x 29 with value < 2^256 -> 8 x u32
-    SRS_HD static fe_t pack(const f29_t &a) {
+    SRS_HD static fe_t pack(const f29_t &a SRS_F29_SITE) {
+        SRS_F29_CHECK(pack(a, site_file, site_line));
         fe_t o;
 #pragma unroll
         for (int w = 0; w < 8; ++w) {
@@ -109,7 +133,7 @@ struct Fp29 {
     }
 
     // carry propagation: limbs < 2^32 in, limbs < 2^29 out (top limb takes the rest); value unchanged
-    SRS_HD static f29_t normalize(const f29_t &a) {
+    SRS_HD static f29_t normalize(const f29_t &a SRS_F29_SITE) {
         f29_t o;
         uint32_t c = 0;
 #pragma unroll
@@ -119,6 +143,7 @@ struct Fp29 {
             c = t >> B;
         }
         o.v[8] = a.v[8] + c;
+        SRS_F29_CHECK(normalize(o, a, site_file, site_line));
         return o;
     }
 
@@ -132,7 +157,7 @@ struct Fp29 {
 #include "field29_chain.inc"
 #else
     // Montgomery product a * b / 2^261 mod p -- see the bounds in the header comment
-    SRS_HD static f29_t mul(const f29_t &a, const f29_t &b) {
+    SRS_HD static f29_t mul(const f29_t &a, const f29_t &b SRS_F29_SITE) {
         uint64_t acc = 0;
         uint32_t m[9];
         f29_t o;
@@ -156,13 +181,14 @@ struct Fp29 {
             acc >>= B;
         }
         o.v[8] = (uint32_t)acc;
+        SRS_F29_CHECK(mul(o, a, b, site_file, site_line));
         return o;
     }
     // (a * b + c * d) / 2^261 mod p with ONE Montgomery reduction: the two products are accumulated column by column into the same
     // 64-bit sums (27 terms per column instead of 18), which needs the tighter limb bounds  a_i, c_i < 2^30,  b_j, d_j < 2^29
     // (18 * 2^59 + 9 * 2^58 < 2^64) and  A * B + C * D < 2^261 * P;  returns a value < 2P with limbs < 2^29.
     // Saves the 81 + 9 multiplier instructions of the second reduction (r03: the Y coordinate of a mixed addition is t r - y ppp).
-    SRS_HD static f29_t mul2(const f29_t &a, const f29_t &b, const f29_t &c, const f29_t &d) {
+    SRS_HD static f29_t mul2(const f29_t &a, const f29_t &b, const f29_t &c, const f29_t &d SRS_F29_SITE) {
         uint64_t acc = 0;
         uint32_t m[9];
         f29_t o;
@@ -190,9 +216,10 @@ struct Fp29 {
             acc >>= B;
         }
         o.v[8] = (uint32_t)acc;
+        SRS_F29_CHECK(mul2(o, a, b, c, d, site_file, site_line));
         return o;
     }
-    SRS_HD static f29_t sqr(const f29_t &a) {
+    SRS_HD static f29_t sqr(const f29_t &a SRS_F29_SITE) {
         // the doubled cross products a_i a_j (i < j) are formed once: 45 + 81 multiply-accumulates instead of 81 + 81
         uint64_t acc = 0;
         uint32_t m[9], a2[9];
@@ -221,6 +248,7 @@ struct Fp29 {
             acc >>= B;
         }
         o.v[8] = (uint32_t)acc;
+        SRS_F29_CHECK(sqr(o, a, site_file, site_line));
         return o;
     }
 
@@ -229,30 +257,34 @@ struct Fp29 {
     // a - b + c p, limb-wise, NOT normalised.  Needs b_i < 2^(29+e) (i < 8), b_8 <= top limb of c p - 2^e,
     // result limbs < a_i + 2^(29+e) + 2^29.
     template <uint32_t CP, uint32_t E>
-    SRS_HD static f29_t sub_lazy(const f29_t &a, const f29_t &b) {
+    SRS_HD static f29_t sub_lazy(const f29_t &a, const f29_t &b SRS_F29_SITE) {
         f29_t o;
 #pragma unroll
         for (int i = 0; i < 9; ++i) o.v[i] = a.v[i] + kpb(CP, E, i) - b.v[i];
+        SRS_F29_CHECK(template sub_lazy<CP, E>(o, &a, b, site_file, site_line));
         return o;
     }
     // c p - b  (negation), same conditions
     template <uint32_t CP, uint32_t E>
-    SRS_HD static f29_t neg_lazy(const f29_t &b) {
+    SRS_HD static f29_t neg_lazy(const f29_t &b SRS_F29_SITE) {
         f29_t o;
 #pragma unroll
         for (int i = 0; i < 9; ++i) o.v[i] = kpb(CP, E, i) - b.v[i];
+        SRS_F29_CHECK(template sub_lazy<CP, E>(o, (const f29_t *)nullptr, b, site_file, site_line));
         return o;
     }
-    SRS_HD static f29_t add_lazy(const f29_t &a, const f29_t &b) {
+    SRS_HD static f29_t add_lazy(const f29_t &a, const f29_t &b SRS_F29_SITE) {
         f29_t o;
 #pragma unroll
         for (int i = 0; i < 9; ++i) o.v[i] = a.v[i] + b.v[i];
+        SRS_F29_CHECK(add_lazy(o, a, b, site_file, site_line));
         return o;
     }
     SRS_HD static f29_t select(bool c, const f29_t &x, const f29_t &y) {
         f29_t o;
 #pragma unroll
         for (int i = 0; i < 9; ++i) o.v[i] = c ? x.v[i] : y.v[i];
+        SRS_F29_CHECK(select(o, x, y));
         return o;
     }
 
@@ -264,7 +296,7 @@ struct Fp29 {
         const uint64_t p_top = ((uint64_t)P::p(7) << 32) | P::p(6);              // P >> 192, truncated: the quotient below is an OVER-estimate by < 2^-60 ...
         return (uint32_t)((((unsigned __int128)1) << 90) / p_top) - 1u;         // ... so one less: never above 2^282 / P
     }
-    SRS_HD static f29_t reduce_lazy(const f29_t &a) {
+    SRS_HD static f29_t reduce_lazy(const f29_t &a SRS_F29_SITE) {
         constexpr uint32_t MQ = quotient_const();
         static_assert(P::p(7) >> 28 != 0 && MQ < (1u << 30), "reduce_lazy: P must have 253-254 bits");
         const uint32_t q = (uint32_t)(((uint64_t)a.v[8] * MQ) >> 50);
@@ -277,11 +309,13 @@ struct Fp29 {
             acc >>= B;                          // arithmetic: the borrow travels as a negative carry
         }
         o.v[8] = (uint32_t)(acc + (int64_t)a.v[8] - (int64_t)((uint64_t)q * p(8)));      // a - q P is in [0, 2P): the top limb ends below 2^23
+        SRS_F29_CHECK(reduce_lazy(o, a, site_file, site_line));
         return o;
     }
 
     // normalised value < 4P  ->  the canonical representative in [0, P), packed
-    SRS_HD static fe_t to_canonical_fe(const f29_t &a) {
+    SRS_HD static fe_t to_canonical_fe(const f29_t &a SRS_F29_SITE) {
+        SRS_F29_CHECK(to_canonical(a, site_file, site_line));
         fe_t x = pack(a);                       // < 4P < 2^256
         using F = Fp<P>;
         // two conditional subtractions of 2P / P on the 8 x 32 form (reduce_once expects < 2p after the first)

@@ -671,6 +671,9 @@ static void plan_sweep(Program &p, const FieldOps &f) {
 
 }  // namespace
 
+// bound (in units of p) to which the partner of a hoisted affine factor is prepared -- see the arithmetic where it is used
+static constexpr double HOIST_PARTNER_BOUND = 8.0;
+
 // the sweep form as C++ (see the comment on the signature below)
 std::string emit_sweep_source(const Program &p, const std::string &name, bool shared_mul) {
     std::string o;
@@ -812,7 +815,12 @@ std::string emit_sweep_source(const Program &p, const std::string &name, bool sh
             double ba, bb;
             if (hoist_of.count(v)) {                             // (q s) * y with the affine factor kept in `aff`
                 const Hoist &h = hoists[hoist_of[v]];
-                std::string c = prep(h.c, lvl(h.c), 12.0, bb);
+                // `aff` is a product (< 2p) plus one step (< 2p) per point passed: < 2p (1 + pt) at point pt, and the sweep form takes
+                // at most DMAX + 1 points -- budgeted as 2p (1 + DMAX + 1) = 20p.  mul needs A * B < (2^261 / p) p^2 = 169.2 p^2 (both
+                // fields), so the partner is prepared to <= 8p: 20 * 8 = 160.  (The general operand bound 12 gives 240: a partner that
+                // is a sum of 9 .. 12 column values broke the multiplier's stated precondition.)
+                static_assert(2.0 * (1 + DMAX + 1) * HOIST_PARTNER_BOUND < 165.0, "hoisted factor * partner must stay below 2^261 / p");
+                std::string c = prep(h.c, lvl(h.c), HOIST_PARTNER_BOUND, bb);
                 o += d + MUL + "aff" + S(v) + ", " + c + ");\n";
                 bound[v] = 2.0;
                 continue;
@@ -953,7 +961,7 @@ std::string emit_sweep_source(const Program &p, const std::string &name, bool sh
             }
             for (int v : cl.loads)
                 if (p.vins[def[v]].op == I_LD_ADV) o += "            l" + S(v) + " = F::add(l" + S(v) + ", s" + S(v) + ");\n";
-            for (const Hoist &h : hoists)                         // < 2p (1 + points): fine as a multiplier operand (<= 20p * 2p < 165 p^2)
+            for (const Hoist &h : hoists)                         // < 2p (1 + points) <= 20p; its partner is prepared to HOIST_PARTNER_BOUND (gen)
                 o += "            aff" + S(h.v) + " = G::normalize(G::add_lazy(aff" + S(h.v) + ", affs" + S(h.v) + "));\n";
             o += "        }\n    }\n";
         } else {

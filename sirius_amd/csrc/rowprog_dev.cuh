@@ -74,9 +74,9 @@ template <class F>
 __device__ __attribute__((noinline)) fe_t sqr_ni(fe_t a) { return F::sqr(a); }
 
 template <class F>
-__device__ __attribute__((noinline)) f29_t mul29_ni(f29_t a, f29_t b) { return Fp29<typename F::Params>::mul(a, b); }
+__device__ __attribute__((noinline)) f29_t mul29_ni(f29_t a, f29_t b SRS_F29_SITE) { return Fp29<typename F::Params>::mul(a, b SRS_F29_SITE_PASS); }
 template <class F>
-__device__ __attribute__((noinline)) f29_t sqr29_ni(f29_t a) { return Fp29<typename F::Params>::sqr(a); }
+__device__ __attribute__((noinline)) f29_t sqr29_ni(f29_t a SRS_F29_SITE) { return Fp29<typename F::Params>::sqr(a SRS_F29_SITE_PASS); }
 
 // column loads (PlonkEvalDomain::eval_column_var / eval_advice_var, src/plonk/eval.rs:57-69,153-228)
 template <class F>
@@ -173,11 +173,13 @@ __device__ __forceinline__ f29_t sw_load(const uint32_t *acc, uint32_t pt) {
     f29_t o;
 #pragma unroll
     for (uint32_t i = 0; i < 9; ++i) o.v[i] = acc[(pt * SW_WORDS + i) * RP_THREADS];
+    SRS_F29_LDS_LOAD(o, acc + pt * SW_WORDS * RP_THREADS);
     return o;
 }
 __device__ __forceinline__ void sw_store(uint32_t *acc, uint32_t pt, const f29_t &x) {
 #pragma unroll
     for (uint32_t i = 0; i < 9; ++i) acc[(pt * SW_WORDS + i) * RP_THREADS] = x.v[i];
+    SRS_F29_LDS_STORE(acc + pt * SW_WORDS * RP_THREADS, x);
 }
 template <class F>
 __device__ __forceinline__ void sw_fold(uint32_t *acc, uint32_t pt, const fe_t &one261) {
