@@ -70,7 +70,8 @@ const char *srs_version(void);
 /* Run-time tunables (csrc/tuning.h holds the table): each selects among code paths the library takes by default for SOME input size
  * (or moves the size threshold between them); none changes a result.  Tests use them to run a large-input path on an input the CPU
  * oracle can check; a deployer may set "msm_wide" = 0 to save 13/16 of a large key's HBM (also: environment SRS_MSM_WIDE=0), or
- * "msm_compact" = 1 before creating a key to halve its 16-bit-window table (8 windows + the curve endomorphism, srs_ck_is_compact).
+ * "msm_compact" = 1 before creating a key to halve its 16-bit-window table (8 windows + the curve endomorphism, srs_ck_is_compact), or
+ * "msm_compact" = 2 for such a key that may also hold a 20-bit table of 7 windows (by the rule of "msm_wide": 15 windows per base in all).
  * Names (srs_tuning_name(i), i = 0, 1, ... until NULL): msm_sort, msm_l0, msm_wide, msm_wide_min, msm_slots, msm_slot_log,
  * msm_expect_ovf, msm_quad_max, commit_chunks, pg_f_eval, pg_g_fft, jit_always, no_jit, msm_compact, pg_compat_tree.  Process-wide; set before the calls they
  * affect (a value is read when a call starts).  rc SRS_ERR_INVALID for an unknown name.  No reference counterpart. */
@@ -189,7 +190,8 @@ int srs_ck_num_shards(const srs_ck *ck);      /* 1 for an ordinary key */
  * out[2] = commits that were run a second time because such parts had not been expected, out[3] = sets on the other flows.
  * Multi-device keys report the sum over their shards. */
 int srs_ck_msm_stats(const srs_ck *ck, uint64_t *out4);
-/* 1 when the key also holds the second, 13-window table of the 20-bit pipeline (keys of >= 2^23 bases: + 81 % key memory; whole
+/* 1 when the key also holds the second table of the 20-bit pipeline, 13 windows -- 7 on a compact key created under "msm_compact" = 2
+ * -- (keys of >= 2^23 bases: + 81 % key memory; whole
  * device-resident MSMs of >= 2^23 scalars use it), 0 when it does not -- by size, by SRS_MSM_WIDE=0, or because the device could not hold
  * it (the key then works on the 16-bit windows alone).  Multi-device keys: 1 when every shard holds it. */
 int srs_ck_has_wide_table(const srs_ck *ck);
@@ -198,6 +200,11 @@ int srs_ck_has_wide_table(const srs_ck *ck);
  * eight windows of the table are phi of the lower eight.  A compact key stores 8 windows instead of 16 (half the HBM, half the
  * expansion at creation), never builds the 20-bit table (MSMs of every size run on the 16-bit windows) and pays one field product
  * per gathered point of the upper half.  Same results, same entries; srs_ck_get_bases / srs_ck_save_file are unchanged.
+ * "msm_compact" = 2 is a compact key that MAY also hold a 20-bit table, by the rule of full keys ("msm_wide" / SRS_MSM_WIDE 0 = never,
+ * 1 = always, unset = keys of >= 2^23 bases; a device that cannot hold it leaves the key compact on the 16-bit windows alone).  A half
+ * of the split scalar is below 2^126, so that table has 7 windows, not 13: such a key holds 8 + 7 = 15 windows per base
+ * (srs_ck_table_bytes = len * 64 * 15, srs_ck_is_compact = srs_ck_has_wide_table = 1), and whole device-resident MSMs of >= 2^23
+ * scalars take 14 digits of 20 bits per scalar instead of 16 of 16 bits.  "msm_compact" = 1 never builds it.
  * srs_ck_is_compact: 1 / 0.  srs_ck_table_bytes: bytes of window tables (16-bit and 20-bit) this rank holds -- all shards of a
  * multi-device key.  No reference counterpart. */
 int srs_ck_is_compact(const srs_ck *ck);

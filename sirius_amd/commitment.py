@@ -124,15 +124,18 @@ class CommitmentKey:
         return dict(h2d_bytes=int(out[0]), peer_bytes=int(out[1]), streamed_commits=int(out[2]), device=int(out[3]))
 
     def has_wide_table(self):
-        """True when the key holds the second (20-bit-window) table (srs_ck_has_wide_table)."""
+        """True when the key holds the second (20-bit-window) table (srs_ck_has_wide_table): 13 windows, or 7 on a compact key created
+        under tuning msm_compact=2."""
         return bool(L.lib().srs_ck_has_wide_table(self._h))
 
     def is_compact(self):
-        """True when the key stores 8 windows and uses the curve endomorphism for the other 8 (created under tuning msm_compact=1)."""
+        """True when the key stores 8 windows and uses the curve endomorphism for the other 8 (created under tuning msm_compact=1, or
+        msm_compact=2: such a key may also hold the 7-window wide table, see has_wide_table)."""
         return bool(L.lib().srs_ck_is_compact(self._h))
 
     def table_bytes(self):
-        """Bytes of window tables this key holds on its device(s) (srs_ck_table_bytes)."""
+        """Bytes of window tables this key holds on its device(s) (srs_ck_table_bytes): 64 per base and window -- 16 (+ 13 wide) windows on a
+        full key, 8 (+ 7 wide under msm_compact=2) on a compact one."""
         return int(L.lib().srs_ck_table_bytes(self._h))
 
     @classmethod

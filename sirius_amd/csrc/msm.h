@@ -49,6 +49,8 @@ constexpr uint32_t SLOT_L0_MIN_LOG = 2, SLOT_L0_MAX_LOG = 16;   // part length 2
 // entries by segment, then every stage of the 16-bit pipeline runs on the 16 segments as a batch.
 constexpr int WBITS_W = 20;
 constexpr int NWIN_W = 13;                // ceil(254 / 20); the top digit has 14 bits + carry
+constexpr int NWIN_WC = 7;                // wide windows a compact key stores: a half of the split scalar is below 2^126 (glv.cuh), so 7 x 20 bits hold it and
+                                          // its top digit (6 bits + carry) never carries out; 14 digit rows per scalar, rows 7..13 gather phi of windows 0..6
 constexpr uint32_t NSEG_W = 16;           // 2^(WBITS_W - 1) / NBUCKET
 constexpr uint32_t WIDE_THREADS = 256, WIDE_PER = 2, WIDE_TILE = WIDE_THREADS * WIDE_PER;   // scalars per workgroup of the segment passes
 // Measured (profiles/r02_wide_windows.txt): the wide pipeline wins from ~8 M scalars (12 * 2^20 uniform: 20.3 vs 22.2 ms);
@@ -67,15 +69,19 @@ inline bool expect_ovf_initial() { return tuning::get_or(tuning::MSM_EXPECT_OVF,
 // A COMPACT key (tuning msm_compact = 1 at creation) holds windows 0..7 only: a scalar is split k = k1 + lambda k2 (glv.cuh), digit rows
 // 0..7 are the digits of |k1|, rows 8..15 those of |k2|, and an entry of rows 8..15 gathers T[(w - 8) * len + i] with PAY_ENDO set:
 // the accumulation multiplies its x by beta.  Everything between the digits and level 0 sees the same 16 rows as for a full key.
+// Created under msm_compact = 2 the key may also carry a wide table (wants_wide_table, as for full keys) -- of NWIN_WC = 7 windows, not 13:
+// the wide flow then takes 7 signed 20-bit digits of |k1| and 7 of |k2| (rows 7..13 flagged PAY_ENDO), 8 + 7 = 15 windows per base in all.
+// msm_compact = 1 never has one.
 struct Key {
     int curve = 0;            // 0 bn256 G1, 1 grumpkin
     size_t len = 0;           // number of bases held by THIS rank
     size_t global_len = 0;    // length of the whole key (== len when world == 1)
     uint32_t rank = 0, world = 1;
     bool compact = false;     // 8-window table + endomorphism (choose_windows, before the table is allocated)
+    bool compact_wide = false;   // a compact key that may carry the 7-window wide table (msm_compact = 2; choose_windows)
     bool compact_scalars = false;   // world > 1: the scalar vectors handed to run() hold ONLY this rank's stripes, gathered (multi-device keys)
     affine_t *table = nullptr;
-    affine_t *table_w = nullptr;   // T_w[w][i] = 2^(20 w) P_i, w < NWIN_W (keys of >= 2^WIDE_MIN_KEY_LOG bases; owned by the key: release())
+    affine_t *table_w = nullptr;   // T_w[w][i] = 2^(20 w) P_i, w < NWIN_W -- w < NWIN_WC on a compact key (keys of >= 2^WIDE_MIN_KEY_LOG bases; owned by the key: release())
     uint64_t stat_slot_sets = 0, stat_hot_sets = 0, stat_redo = 0, stat_other_sets = 0;   // srs_ck_msm_stats
     uint64_t last_entries = 0;        // non-zero digits (= bucket additions) of the last commit that ran in slot mode (note_commit) ...
     uint64_t last_scalars = 0;        // ... and its scalars (both set by note_commit, both 0 when the commit had no slot-mode set): the density the next streamed commit's chunk cuts are chosen for
@@ -102,7 +108,7 @@ struct Key {
 // decides the key's form from tuning msm_compact (read HERE, once per key) and returns the windows `table` must hold: every creation
 // entry allocates len * choose_windows(key) entries, fills window 0 and calls build_table
 int choose_windows(Key &k);
-// fills table[len .. windows * len) from table[0 .. len); full keys that want it (wants_wide_table) also get table_w
+// fills table[len .. windows * len) from table[0 .. len); full keys and msm_compact = 2 keys that want it (wants_wide_table) also get table_w
 void build_table(Key &k, hipStream_t stream);
 // bytes of window tables the key holds (table and table_w)
 size_t table_bytes(const Key &k);

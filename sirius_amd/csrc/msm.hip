@@ -33,7 +33,8 @@
 // take the 13 x 20-bit "wide" windows over a second table (16 virtual MSMs of 2^15 buckets each).
 // Compact keys (tuning msm_compact = 1 at creation, msm.h): 8 stored windows; k_digits splits the scalar with the curve endomorphism
 // (glv.cuh), rows 8..15 gather phi of windows 0..7 -- the payload carries a flag, level 0 multiplies the gathered x by beta (k_accum0c /
-// k_accum0sc).  Everything between the digits and level 0, and everything after it, is shared with full keys.
+// k_accum0sc).  Everything between the digits and level 0, and everything after it, is shared with full keys.  msm_compact = 2: such a
+// key may also hold a wide table of 7 windows; the segment passes then split the scalar themselves (k_seg_pass<., ., true>: 14 rows).
 // Host driver (end of this file): enqueue() picks one of three flows (enqueue_t: levels, enqueue_slots_t: slot mode, enqueue_wide_t).  Each
 // computes its shape once (*_shape: sizes, grids and every tunable), carves the key's arena by its one buffer list (*_layout, also the
 // sizer behind reserve()) and runs the shared stages: sort_front, accum_levels, reduce_buckets, land.
@@ -201,22 +202,35 @@ struct BatchDesc {
     uint32_t base[BATCH_ARGS];      // first base of MSM m inside the key (0 for the usual prefix commit; chunked commits slide it)
 };
 
-// compact keys: the 8 signed 16-bit digits of one half (|k| < 2^127, sign `neg`) of the split scalar, rows d[0], d[n], ..., d[7 n].
-// The half's sign goes into every digit, and the tie v = 0x8000 is broken by it: the code format holds digits -0x7FFF .. 0x8000, so a
-// negative half recodes |k| into -0x8000 .. 0x7FFF before negating.  The top digit never carries out (|k| < 2^127: its v <= 0x8000 only
-// when the bound were 2^127 itself; tools/gen_glv_consts.py proves < 2^126).
-__device__ __forceinline__ void recode_half(const uint32_t (&k)[4], bool neg, uint16_t *__restrict__ d, size_t n) {
-    const uint32_t top = neg ? 0x7FFFu : 0x8000u;     // largest v that stays a non-negative digit of |k|
+// compact keys: the NW signed WB-bit digits of one half (|k| < 2^127, sign `neg`) of the split scalar; put(w, mag, minus) takes digit w
+// as its magnitude (0: a zero digit) and sign.  The half's sign goes into every digit, and the tie v = 2^(WB - 1) is broken by it: the
+// code formats hold digits -(2^(WB - 1) - 1) .. 2^(WB - 1), so a negative half recodes |k| into -2^(WB - 1) .. 2^(WB - 1) - 1 before
+// negating.  The top digit never carries out: tools/gen_glv_consts.py proves |k| < 2^126, so the top window of 8 x 16 bits holds at most
+// 14 bits and that of 7 x 20 bits at most 6, plus the carry.
+template <int WB, int NW, class Put>
+__device__ __forceinline__ void recode_half(const uint32_t (&k)[4], bool neg, Put put) {
+    static_assert(WB * NW >= 127 && WB <= 31, "the windows cover a half of the split scalar");
+    constexpr uint32_t HALF = 1u << (WB - 1);
+    const uint32_t top = neg ? HALF - 1u : HALF;      // largest v that stays a non-negative digit of |k|
     uint32_t carry = 0;
 #pragma unroll
-    for (int w = 0; w < NWIN_COMPACT; ++w) {
-        const uint32_t v = ((k[w >> 1] >> ((w & 1) * 16)) & 0xFFFFu) + carry;
+    for (int w = 0; w < NW; ++w) {
+        const int bit = WB * w, limb = bit >> 5, sh = bit & 31;
+        uint32_t raw = k[limb] >> sh;
+        if (sh + WB > 32 && limb + 1 < 4) raw |= k[limb + 1] << (32 - sh);
+        const uint32_t v = (raw & (2u * HALF - 1u)) + carry;
         const bool borrow = v > top;
-        const uint32_t mag = borrow ? 0x10000u - v : v;
+        const uint32_t mag = borrow ? 2u * HALF - v : v;
         const bool minus = borrow != neg;              // sign of the digit of the SIGNED half
         carry = borrow ? 1u : 0u;
-        d[(size_t)w * n] = (uint16_t)(mag ? ((mag - 1u) | (minus ? 0x8000u : 0u)) : 0xFFFFu);
+        put(w, mag, minus);
     }
+}
+// ... as rows d[0], d[n], ..., d[7 n] of the 16-bit code format
+__device__ __forceinline__ void recode_half16(const uint32_t (&k)[4], bool neg, uint16_t *__restrict__ d, size_t n) {
+    recode_half<WBITS, NWIN_COMPACT>(k, neg, [&](int w, uint32_t mag, bool minus) {
+        d[(size_t)w * n] = (uint16_t)(mag ? ((mag - 1u) | (minus ? 0x8000u : 0u)) : 0xFFFFu);
+    });
 }
 
 template <class C, bool COMPACT>
@@ -236,8 +250,8 @@ __global__ void k_digits(BatchDesc bd, uint16_t *__restrict__ dig, size_t dig_st
     uint16_t *d = dig + (size_t)m * dig_stride;
     if (COMPACT) {                            // k = k1 + lambda k2: rows 0..7 from |k1|, rows 8..15 from |k2| (entries of phi(P), see k_scatter)
         const glv_t g = glv_decompose<C>(s);
-        recode_half(g.k1, g.neg1, d + i, n);
-        recode_half(g.k2, g.neg2, d + (size_t)NWIN_COMPACT * n + i, n);
+        recode_half16(g.k1, g.neg1, d + i, n);
+        recode_half16(g.k2, g.neg2, d + (size_t)NWIN_COMPACT * n + i, n);
         return;
     }
     uint32_t carry = 0;
@@ -593,16 +607,26 @@ struct WideDesc {
     int is_mont;
 };
 
-template <class C>
-__device__ __forceinline__ void wide_codes(const WideDesc &wd, uint32_t i, uint32_t (&code)[NWIN_W]) {
+// digit rows per scalar of the wide flow: 13 windows of the scalar, or (compact key) 7 of |k1| then 7 of |k2|
+constexpr int wide_digits(bool compact) { return compact ? 2 * NWIN_WC : NWIN_W; }
+
+template <class C, bool COMPACT>
+__device__ __forceinline__ void wide_codes(const WideDesc &wd, uint32_t i, uint32_t (&code)[wide_digits(COMPACT)]) {
     using S = typename C::S;
     if (i >= wd.n) {
 #pragma unroll
-        for (int w = 0; w < NWIN_W; ++w) code[w] = 0xFFFFFFFFu;
+        for (int w = 0; w < wide_digits(COMPACT); ++w) code[w] = 0xFFFFFFFFu;
         return;
     }
     fe_t s = wd.ptr[Stripes{wd.rank, wd.world}.global_index((size_t)i)];
     if (wd.is_mont) s = S::from_mont(s);
+    if constexpr (COMPACT) {                  // k = k1 + lambda k2: rows 0..6 from |k1|, rows 7..13 from |k2| (entries of phi(P), see k_seg_pass)
+        const glv_t g = glv_decompose<C>(s);
+        const auto put = [&](int w, uint32_t mag, bool minus) { code[w] = mag ? ((mag - 1u) | (minus ? 0x80000000u : 0u)) : 0xFFFFFFFFu; };
+        recode_half<WBITS_W, NWIN_WC>(g.k1, g.neg1, put);
+        recode_half<WBITS_W, NWIN_WC>(g.k2, g.neg2, [&](int w, uint32_t mag, bool minus) { put(NWIN_WC + w, mag, minus); });
+        return;
+    }
     uint32_t carry = 0;
 #pragma unroll
     for (int w = 0; w < NWIN_W; ++w) {
@@ -620,33 +644,54 @@ __device__ __forceinline__ void wide_codes(const WideDesc &wd, uint32_t i, uint3
     }
 }
 
+// atomicAdd(ctr, 1) for the lanes with `on` set when they all name the SAME LDS counter: one atomic per wavefront (the leader reserves
+// the wavefront's slots, a lane's slot follows from the lanes below it) instead of up to 64 serialised ones.  Wave-uniform control flow
+// only.  Returns the lane's slot (meaningless where !on).  For the hot top windows of a compact key's wide flow (msm.h NWIN_WC).
+__device__ __forceinline__ uint32_t wave_take(uint32_t *ctr, bool on) {
+    const unsigned long long m = __ballot(on ? 1 : 0);
+    if (m == 0) return 0u;
+    const uint32_t lane = threadIdx.x & 63u;
+    const int leader = __ffsll(m) - 1;
+    uint32_t first = 0;
+    if ((int)lane == leader) first = atomicAdd(ctr, (uint32_t)__popcll(m));
+    first = __shfl(first, leader, 64);
+    return first + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+}
+
 // The two segment passes over the scalars (the digits are recomputed rather than stored: 32 B read per scalar instead of
-// 52 B written and read).  A workgroup takes WIDE_TILE scalars = up to 6656 entries; the 16 segment counters are kept per
+// 52 B written and read).  A workgroup takes WIDE_TILE scalars = up to 6656 entries (7168 on a compact key); the 16 segment counters are kept per
 // wavefront in LDS (64 words = 64 banks), so an atomic only meets the lanes of its own wavefront.
 //   GROUP = false: tile_cnt[v][tile] = entries of the tile in segment v; seg_total[v] += the same
 //   GROUP = true : tile_cnt holds the scanned offsets (k_seg_scan): the tile's entries are ordered by segment in LDS (the
 //                  returning atomic is the entry's rank) and leave as 16 coalesced runs of
 //                  (key = low 15 bits of the bucket, payload = table index | sign << 31)
-template <class C, bool GROUP>
+// COMPACT (a compact key with the 7-window table, msm.h): 14 digit rows, row w gathers window w % 7 and rows 7..13 carry PAY_ENDO -- the
+// staging is sized from the digit count (512 x 14 entries, 43 KB).  Instantiations of their own: what full keys launch is compiled as before.
+template <class C, bool GROUP, bool COMPACT>
 __global__ void SRS_KERNEL_BOUNDS(WIDE_THREADS, 1)
     k_seg_pass(WideDesc wd, uint32_t *__restrict__ tile_cnt, uint32_t T, uint32_t *__restrict__ seg_total,
                uint16_t *__restrict__ gkey, uint32_t *__restrict__ gpay, uint32_t table_stride) {
-    constexpr uint32_t NW = WIDE_THREADS / 64, STAGE = GROUP ? WIDE_TILE * NWIN_W : 1;
+    constexpr int ND = wide_digits(COMPACT);
+    constexpr uint32_t NW = WIDE_THREADS / 64, STAGE = GROUP ? WIDE_TILE * ND : 1;
     __shared__ uint32_t wc[NW][NSEG_W];          // counts, then (GROUP) the next free staging slot of (wavefront, segment)
     __shared__ uint32_t ss[NSEG_W + 1], goff[NSEG_W];
     __shared__ uint16_t skey[STAGE];
     __shared__ uint32_t spay[STAGE];
     const uint32_t tile = blockIdx.x, wave = threadIdx.x >> 6;
     if (threadIdx.x < NW * NSEG_W) (&wc[0][0])[threadIdx.x] = 0;
-    uint32_t code[WIDE_PER][NWIN_W];
+    uint32_t code[WIDE_PER][ND];
 #pragma unroll
-    for (uint32_t k = 0; k < WIDE_PER; ++k) wide_codes<C>(wd, tile * WIDE_TILE + k * WIDE_THREADS + threadIdx.x, code[k]);
+    for (uint32_t k = 0; k < WIDE_PER; ++k) wide_codes<C, COMPACT>(wd, tile * WIDE_TILE + k * WIDE_THREADS + threadIdx.x, code[k]);
     __syncthreads();
 #pragma unroll
     for (uint32_t k = 0; k < WIDE_PER; ++k) {
 #pragma unroll
-        for (int w = 0; w < NWIN_W; ++w) {
+        for (int w = 0; w < ND; ++w) {
             const uint32_t c = code[k][w];
+            if (COMPACT && (w + 1) % NWIN_WC == 0) {          // a half's top digit is <= 2^6: always segment 0, from every lane
+                wave_take(&wc[wave][0], c != 0xFFFFFFFFu);
+                continue;
+            }
             if (c != 0xFFFFFFFFu) atomicAdd(&wc[wave][(c >> 15) & (NSEG_W - 1)], 1u);
         }
     }
@@ -689,12 +734,16 @@ __global__ void SRS_KERNEL_BOUNDS(WIDE_THREADS, 1)
     for (uint32_t k = 0; k < WIDE_PER; ++k) {
         const uint32_t i = tile * WIDE_TILE + k * WIDE_THREADS + threadIdx.x;
 #pragma unroll
-        for (int w = 0; w < NWIN_W; ++w) {
+        for (int w = 0; w < ND; ++w) {
             const uint32_t c = code[k][w];
+            const bool top = COMPACT && (w + 1) % NWIN_WC == 0;
+            const uint32_t pos_top = top ? wave_take(&wc[wave][0], c != 0xFFFFFFFFu) : 0u;
             if (c != 0xFFFFFFFFu) {
-                const uint32_t pos = atomicAdd(&wc[wave][(c >> 15) & (NSEG_W - 1)], 1u);
+                const uint32_t pos = top ? pos_top : atomicAdd(&wc[wave][(c >> 15) & (NSEG_W - 1)], 1u);
                 skey[pos] = (uint16_t)(c & 0x7FFFu);
-                spay[pos] = ((uint32_t)w * table_stride + wd.base + i) | (c & 0x80000000u);
+                const uint32_t row = COMPACT ? ((uint32_t)w % NWIN_WC * table_stride + wd.base) | (w >= NWIN_WC ? PAY_ENDO : 0u)
+                                             : (uint32_t)w * table_stride + wd.base;
+                spay[pos] = (row + i) | (c & 0x80000000u);
             }
         }
     }
@@ -818,6 +867,9 @@ __global__ void SRS_KERNEL_BOUNDS(1024, 1)
     }
 }
 
+// HOT0 (compact keys): sub-segment 0 of segment 0 holds the two top digit rows -- 1/7 of ALL entries, 3/4 of that segment's: its
+// counter is taken once per wavefront (wave_take).  An instantiation of its own; full keys launch k_group_g<false>, compiled as before.
+template <bool HOT0>
 __global__ void SRS_KERNEL_BOUNDS(SORT_THREADS, 1)
     k_group_g(const uint16_t *__restrict__ gkey, const uint32_t *__restrict__ gpay, const uint32_t *__restrict__ seg_off,
               const uint32_t *__restrict__ tile_base, const uint32_t *__restrict__ tile_hist, uint16_t *__restrict__ gkey2,
@@ -840,7 +892,15 @@ __global__ void SRS_KERNEL_BOUNDS(SORT_THREADS, 1)
             pay[k] = i < hi ? gpay[i] : 0u;
         }
 #pragma unroll
-        for (uint32_t k = 0; k < GRP_PER; ++k) rank[k] = key[k] != 0xFFFFu ? atomicAdd(&cnt[key[k] / SEG_BUCKETS], 1u) : 0u;
+        for (uint32_t k = 0; k < GRP_PER; ++k) {
+            if (HOT0 && v == 0) {                                       // workgroup-uniform
+                const bool hot = key[k] < SEG_BUCKETS;                  // (a padding key is 0xFFFF)
+                const uint32_t r = wave_take(&cnt[0], hot);
+                rank[k] = hot ? r : key[k] != 0xFFFFu ? atomicAdd(&cnt[key[k] / SEG_BUCKETS], 1u) : 0u;
+            } else {
+                rank[k] = key[k] != 0xFFFFu ? atomicAdd(&cnt[key[k] / SEG_BUCKETS], 1u) : 0u;
+            }
+        }
         __syncthreads();
         uint32_t n_sub;
         const uint32_t ex = block_exclusive_scan(tid < SEG ? cnt[tid] : 0u, sc, &n_sub);
@@ -1797,15 +1857,19 @@ static void build_table_t(Key &k, hipStream_t stream) {
     xyzz_t *tmp = nullptr;
     SRS_HIP_CHECK(hipMalloc((void **)&tmp, (size_t)n * sizeof(xyzz_t)));
     // the second table is an optimisation (+81 % key memory): a device that cannot hold it keeps the 16-bit windows for everything
-    // (use_wide() is false without table_w; srs_ck_has_wide_table tells).  A compact key is the memory-saving form: it never has one.
-    if (!k.compact && wants_wide_table(n) && hipMalloc((void **)&k.table_w, (size_t)n * NWIN_W * sizeof(affine_t)) != hipSuccess) {
+    // (use_wide() is false without table_w; srs_ck_has_wide_table tells).  A compact key created under msm_compact = 1 is the memory-saving
+    // form: it never has one.  Under msm_compact = 2 it takes the table by the same rule as a full key, with 7 windows instead of 13 (a half
+    // of the split scalar is below 2^126).
+    const int nwin_w = k.compact ? NWIN_WC : NWIN_W;
+    if ((!k.compact || k.compact_wide) && wants_wide_table(n) &&
+        hipMalloc((void **)&k.table_w, (size_t)n * nwin_w * sizeof(affine_t)) != hipSuccess) {
         (void)hipGetLastError();
         k.table_w = nullptr;
     }
     if (k.table_w) {
         SRS_HIP_CHECK(hipMemcpyAsync(k.table_w, k.table, (size_t)n * sizeof(affine_t), hipMemcpyDeviceToDevice, stream));
-        expand_windows<C>(k.table_w, n, NWIN_W, WBITS_W, tmp, stream);
-        const size_t total_w = (size_t)n * NWIN_W;
+        expand_windows<C>(k.table_w, n, nwin_w, WBITS_W, tmp, stream);
+        const size_t total_w = (size_t)n * nwin_w;
         SRS_LAUNCH((k_table_form<C>), (ceil_div(total_w, 256)), (256), 0, stream, k.table_w, total_w);
     }
     const int nwin = k.compact ? NWIN_COMPACT : NWIN;
@@ -1856,18 +1920,22 @@ void build_table(Key &k, hipStream_t stream) {
 }
 
 int choose_windows(Key &k) {
-    k.compact = tuning::get_or(tuning::MSM_COMPACT, 0) == 1;
-    // the largest index, NWIN_COMPACT * len - 1, must lie below the endomorphism flag of an entry.  A guard: every creation entry already
-    // refuses keys above 2^27 bases (capi.hip), and 8 x 2^27 = 2^30 still fits, so this cannot fire while that limit stands.
+    const int64_t mode = tuning::get_or(tuning::MSM_COMPACT, 0);
+    k.compact = mode == 1 || mode == 2;
+    k.compact_wide = mode == 2;              // may carry the 7-window wide table (build_table: wants_wide_table)
+    // the largest index, NWIN_COMPACT * len - 1, must lie below the endomorphism flag of an entry (the wide table's NWIN_WC * len - 1 is
+    // smaller).  A guard: every creation entry already refuses keys above 2^27 bases (capi.hip), and 8 x 2^27 = 2^30 still fits, so this
+    // cannot fire while that limit stands.
+    static_assert(NWIN_WC <= NWIN_COMPACT, "choose_windows: the guard covers the wide table's payloads");
     if (k.compact && (uint64_t)NWIN_COMPACT * k.len > PAY_ENDO) {
-        set_error("compact key (msm_compact = 1): 8 x " + std::to_string(k.len) + " table entries do not fit below the endomorphism flag (2^30)");
+        set_error("compact key (msm_compact = 1 / 2): 8 x " + std::to_string(k.len) + " table entries do not fit below the endomorphism flag (2^30)");
         throw DeviceError{4};      // SRS_ERR_INVALID
     }
     return k.compact ? NWIN_COMPACT : NWIN;
 }
 size_t table_bytes(const Key &k) {
     if (!k.table) return 0;
-    return k.len * sizeof(affine_t) * ((k.compact ? NWIN_COMPACT : NWIN) + (k.table_w ? NWIN_W : 0));
+    return k.len * sizeof(affine_t) * ((k.compact ? NWIN_COMPACT : NWIN) + (k.table_w ? (k.compact ? NWIN_WC : NWIN_W) : 0));
 }
 
 // ---- host driver: three flows (16-bit windows with levels / in slot mode, wide windows) over shared stages -----------------------
@@ -1940,7 +2008,7 @@ struct SetShape : LevelShape { // the two flows of the 16-bit windows: + their c
 };
 struct NarrowShape : SetShape { uint32_t l0_log; };         // log2 of the part length (slot mode chooses it on the device: k_plan_s)
 struct SlotShape : SetShape { uint32_t S, nred; };          // slots per bucket; reduction levels at the end of a commit (8 inputs per output)
-struct WideShape : LevelShape { uint32_t l0_log, T, tiles_g; };   // log2 of the part length; workgroups of the segment passes, of the sort inside the segments
+struct WideShape : LevelShape { uint32_t l0_log, T, tiles_g; };   // log2 of the part length; workgroups of the segment passes, of the sort inside the segments (M = n x the key's digit rows)
 
 static void sort_shape(SetShape &h, uint32_t n_max, uint32_t batch) {
     h.M = (uint64_t)n_max * NWIN;
@@ -1977,12 +2045,15 @@ static SlotShape slot_shape(uint32_t n_max, uint32_t batch) {
     h.plan_stride = (size_t)(h.levels + 2) * (NBUCKET + 1) + 4;
     return h;
 }
-static WideShape wide_shape(uint32_t n) {
+static WideShape wide_shape(uint32_t n, uint32_t digits /* rows per scalar: wide_digits(key is compact) */) {
     WideShape w;
-    w.M = (uint64_t)n * NWIN_W;
+    w.M = (uint64_t)n * digits;
     w.quad_max = acc1_quad_max();
     w.l0_log = l0_log_for(w.M);
-    w.levels = levels_for((w.M + (1ull << w.l0_log) - 1) >> w.l0_log);      // worst case: every entry in one bucket of one segment
+    // worst case: every entry in one bucket of one segment.  That also bounds the hot top windows of a compact key (each half's seventh
+    // digit is at most 2^6, so 2 of the 14 rows fall into <= 65 buckets of segment 0: n / 32 entries per bucket for uniform scalars, against
+    // the 14 n this is sized for): k_plan finds <= FINAL_FANIN parts left for the wave-level pass within these levels
+    w.levels = levels_for((w.M + (1ull << w.l0_log) - 1) >> w.l0_log);
     w.plan_stride = (size_t)(w.levels + 1) * (NBUCKET + 1) + 4;
     w.cap0 = (w.M >> w.l0_log) + (uint64_t)NSEG_W * (NBUCKET + 1);
     w.cap1 = w.cap0 / ACC_L1 + (uint64_t)NSEG_W * (NBUCKET + 1);
@@ -2106,8 +2177,8 @@ size_t workspace_bytes(uint32_t n_max, uint32_t batch) {
 static size_t workspace_bytes_slots(uint32_t n_max, uint32_t batch) {
     return sized([&](auto &A) { return slot_layout(A, slot_shape(n_max, batch), batch); });
 }
-static size_t workspace_bytes_wide(uint32_t n) {
-    return sized([&](auto &A) { return wide_layout(A, wide_shape(n)); });
+static size_t workspace_bytes_wide(uint32_t n, uint32_t digits) {
+    return sized([&](auto &A) { return wide_layout(A, wide_shape(n, digits)); });
 }
 
 // ---- shared stages --------------------------------------------------------------------------------------------------------------
@@ -2371,7 +2442,12 @@ static bool use_wide(const Key &k, uint32_t n_max, uint32_t batch) {
 
 template <class C>
 static bool enqueue_wide_t(Key &k, const fe_t *scalars_dev, uint32_t n, uint32_t base, int is_mont, hipStream_t stream, uint32_t slot) {
-    const WideShape w = wide_shape(n);
+    const WideShape w = wide_shape(n, wide_digits(k.compact));
+    // a compact key differs in the two segment passes (split digits, 14 rows, flagged payloads), in the hot sub-segment of k_group_g and in level 0
+    const auto seg_count = k.compact ? &k_seg_pass<C, false, true> : &k_seg_pass<C, false, false>;
+    const auto seg_group = k.compact ? &k_seg_pass<C, true, true> : &k_seg_pass<C, true, false>;
+    const auto group_g = k.compact ? &k_group_g<true> : &k_group_g<false>;
+    const auto accum0 = k.compact ? &k_accum0c<C> : &k_accum0<C>;
     const WideBufs b = carve(k.arena, [&](auto &A) { return wide_layout(A, w); });
     uint32_t *seg_total = b.seg3, *seg_off = b.seg3 + (NSEG_W + 2), *tile_base = b.seg3 + 2 * (NSEG_W + 2), *tile_base2 = b.seg3 + 3 * (NSEG_W + 2);
 
@@ -2387,18 +2463,18 @@ static bool enqueue_wide_t(Key &k, const fe_t *scalars_dev, uint32_t n, uint32_t
     // sort: segment counts -> offsets -> grouping (MSD pass), then the counting sort inside the segments
     SRS_HIP_CHECK(hipMemsetAsync(seg_total, 0, (NSEG_W + 1) * sizeof(uint32_t), stream));
     SRS_HIP_CHECK(hipMemsetAsync(b.count, 0, (size_t)NSEG_W * NBUCKET * sizeof(uint32_t), stream));
-    SRS_LAUNCH((k_seg_pass<C, false>), (w.T), (WIDE_THREADS), 0, stream, wd, b.tile_cnt, w.T, seg_total, (uint16_t *)nullptr,
+    SRS_LAUNCH(seg_count, (w.T), (WIDE_THREADS), 0, stream, wd, b.tile_cnt, w.T, seg_total, (uint16_t *)nullptr,
                (uint32_t *)nullptr, table_stride);
     const uint32_t small_tiles = (w.M >> 19) < 64 ? 1u : 0u, tile2_host = small_tiles ? SORT_TILE2 / 4 : SORT_TILE2;
     SRS_LAUNCH(k_seg_scan, (NSEG_W), (1024), 0, stream, b.tile_cnt, w.T, (const uint32_t *)seg_total, seg_off, tile_base, tile_base2, small_tiles);
-    SRS_LAUNCH((k_seg_pass<C, true>), (w.T), (WIDE_THREADS), 0, stream, wd, b.tile_cnt, w.T, seg_total, b.gkey, b.gpay, table_stride);
+    SRS_LAUNCH(seg_group, (w.T), (WIDE_THREADS), 0, stream, wd, b.tile_cnt, w.T, seg_total, b.gkey, b.gpay, table_stride);
     SRS_LAUNCH(k_hist_g, (w.tiles_g), (SORT_THREADS), 0, stream, (const uint16_t *)b.gkey, (const uint32_t *)seg_off,
                (const uint32_t *)tile_base, b.count, b.tile_hist);
     SRS_LAUNCH(k_plan, (NSEG_W, w.levels + 1), (PLAN_THREADS), 0, stream, (const uint32_t *)b.count, b.cursor, b.plan, w.plan_stride, w.levels,
                w.l0_log, (uint32_t)ACC_L1_LOG, (const uint32_t *)seg_off);
     SRS_LAUNCH(k_scan_seg_g, (SEG, NSEG_W), (1024), 0, stream, b.tile_hist, w.tiles_g, (const uint32_t *)tile_base, (const uint32_t *)b.plan,
                w.plan_stride);
-    SRS_LAUNCH(k_group_g, (w.tiles_g), (SORT_THREADS), 0, stream, (const uint16_t *)b.gkey, (const uint32_t *)b.gpay, (const uint32_t *)seg_off,
+    SRS_LAUNCH(group_g, (w.tiles_g), (SORT_THREADS), 0, stream, (const uint16_t *)b.gkey, (const uint32_t *)b.gpay, (const uint32_t *)seg_off,
                (const uint32_t *)tile_base, (const uint32_t *)b.tile_hist, b.gkey2, b.gpay2);
     // tiles of SORT_TILE2 entries cut per segment: at most M / SORT_TILE2 + NSEG_W of them; 8 x ceil(. / 8) workgroups (XCD mapping)
     SRS_LAUNCH(k_scatter2_g, (8 * ceil_div(ceil_div(w.M, tile2_host) + NSEG_W, 8)), (SORT_THREADS), 0, stream, (const uint16_t *)b.gkey2,
@@ -2407,7 +2483,7 @@ static bool enqueue_wide_t(Key &k, const fe_t *scalars_dev, uint32_t n, uint32_t
     // from here on the 16 segments are ONE linked batch: no strides, the link says where a segment's parts start
     const Parts p{b.plan, w.plan_stride, b.ping, 0, b.pong, 0, b.link};
     SRS_LAUNCH(k_expand, (NBUCKET / 4, NSEG_W), (256), 0, stream, p.plan, p.plan_stride, b.tb, (size_t)0, p.link, 1u);
-    SRS_LAUNCH_TIMED("msm_accum0", n, (k_accum0<C>), (ceil_div(w.cap0, ACC_THREADS)), (ACC_THREADS), 0, stream, (const uint32_t *)b.sorted,
+    SRS_LAUNCH_TIMED("msm_accum0", n, accum0, (ceil_div(w.cap0, ACC_THREADS)), (ACC_THREADS), 0, stream, (const uint32_t *)b.sorted,
                      (size_t)0, p.plan, p.plan_stride, (const uint16_t *)b.tb, (size_t)0, (const affine_t *)k.table_w, p.ping, (size_t)0,
                      1u << w.l0_log, p.link);
     accum_levels<C>(p, w, (uint64_t)NSEG_W * (NBUCKET + 1), 1, stream);
@@ -2486,7 +2562,8 @@ void finish(Key &k, uint32_t batch, uint32_t slot, bool launched, xyzz_t *result
     if (k.curve == 0) finish_t<Bn256>(k, batch, slot, launched, result_host); else finish_t<Grumpkin>(k, batch, slot, launched, result_host);
 }
 void reserve(Key &k, uint32_t n_max, uint32_t batch) {
-    size_t b = use_wide(k, n_max, batch) ? std::max(workspace_bytes_wide(n_max), workspace_bytes(n_max, batch)) : workspace_bytes(n_max, batch);
+    size_t b = use_wide(k, n_max, batch) ? std::max(workspace_bytes_wide(n_max, wide_digits(k.compact)), workspace_bytes(n_max, batch))
+                                         : workspace_bytes(n_max, batch);
     if (batch == 1) b = std::max(b, workspace_bytes_slots(n_max, batch));        // (a chunked commit's sets: slot mode)
     k.arena.reserve(b);
 }

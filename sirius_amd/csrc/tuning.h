@@ -25,7 +25,7 @@ enum Id : int {
     PG_G_FFT,           // 1: compute_G on the roots of unity + ifft (the path of L >= 2 incoming traces) instead of integer points
     JIT_ALWAYS,         // 1: run-time compile the sweep kernels below k = 14 as well
     NO_JIT,             // 1: never call hiprtc (also: environment SRS_NO_JIT, for deployments without the hiprtc library)
-    MSM_COMPACT,        // 0 full key (16 windows) | 1 compact key: 8 windows + the curve endomorphism (half the key's HBM, no 20-bit table); read when a key is created
+    MSM_COMPACT,        // 0 full key (16 windows) | 1 compact key: 8 windows + the curve endomorphism (half the key's HBM, no 20-bit table) | 2 compact key that may also hold a 7-window 20-bit table (msm_wide's rule; 15 windows per base); read when a key is created
     PG_COMPAT_TREE,     // 1: the reference's leaf rows (reference_compat) through the hoisted leaf passes and the weighted trees instead of the closed-form sums
     N_TUNABLES
 };
