@@ -73,7 +73,7 @@ const char *srs_version(void);
  * "msm_compact" = 1 before creating a key to halve its 16-bit-window table (8 windows + the curve endomorphism, srs_ck_is_compact), or
  * "msm_compact" = 2 for such a key that may also hold a 20-bit table of 7 windows (by the rule of "msm_wide": 15 windows per base in all).
  * Names (srs_tuning_name(i), i = 0, 1, ... until NULL): msm_sort, msm_l0, msm_wide, msm_wide_min, msm_slots, msm_slot_log,
- * msm_expect_ovf, msm_quad_max, commit_chunks, pg_f_eval, pg_g_fft, jit_always, no_jit, msm_compact, pg_compat_tree.  Process-wide; set before the calls they
+ * msm_expect_ovf, msm_quad_max, commit_chunks, pg_f_eval, pg_g_fft, jit_always, no_jit, msm_compact, pg_compat_tree, pg_jit_force, pg_jit_waves.  Process-wide; set before the calls they
  * affect (a value is read when a call starts).  rc SRS_ERR_INVALID for an unknown name.  No reference counterpart. */
 int srs_tuning_set(const char *name, int64_t value);
 int srs_tuning_get(const char *name, int64_t *value);        /* *value = INT64_MIN while unset */
@@ -345,7 +345,23 @@ size_t srs_structure_program_source(srs_structure *S, int which, char *buf, size
  * Returns SRS_KERNEL_INTERPRETER, SRS_KERNEL_AHEAD_OF_TIME or SRS_KERNEL_RUNTIME_COMPILED; -1 for a bad argument. */
 enum { SRS_KERNEL_INTERPRETER = 0, SRS_KERNEL_AHEAD_OF_TIME = 1, SRS_KERNEL_RUNTIME_COMPILED = 2 };
 int srs_structure_kernel_kind(const srs_structure *S, int which);
-/* Developer hook, host only (needs no device): compiles a small row program in the emitted form with hiprtc against the device
+/* ProtoGalaxy leaf kernels for ANY gate set.  The leaves of a gate set without ahead-of-time kernels run on the interpreter until its
+ * leaf kernels have been compiled with hiprtc -- never at srs_structure_create (callers of the reference's leaf rows, reference_compat,
+ * evaluate every gate once and must pay nothing), but once per structure:
+ *   - by the first ProtoGalaxy call that runs leaves over the INTENDED rows (reference_compat = 0) on a bn256::Fr structure of >= 2^14
+ *     rows (tuning "jit_always": >= 2^10), unless tuning "no_jit" / SRS_NO_JIT; that call carries the compile (several seconds -- 2.4 s for MainGate [2], 5.8 s for a degree-15 pair measured -- and growing with the gates' size);
+ *   - or here, ahead of the first prove, under the same rule without the 2^14 clause: call it beside srs_structure_create when the
+ *     caller will use the intended rows.
+ * Returns 0 when the structure now has (or already had) compiled or ahead-of-time leaf kernels; SRS_ERR_UNSUPPORTED with the reason in
+ * srs_last_error() when the rule excludes it (wrong field, < 2^10 rows, no_jit, gate programs above the size a unit is compiled for);
+ * SRS_ERR_INVALID and the compiler log (log may be NULL) when the compile failed -- the structure then stays on the interpreter, as
+ * with cross terms, and results are identical either way.  *compile_seconds (may be NULL): hiprtc's time in this call, 0 when nothing
+ * was compiled.  srs_structure_kernel_kind(S, 2) reports SRS_KERNEL_RUNTIME_COMPILED afterwards.  Under reference_compat such a
+ * structure keeps the hoisted interpreter pass.  Tuning "pg_jit_force" = 1 (developer) compiles and uses the kernels also for a gate
+ * set that has ahead-of-time ones. */
+int srs_structure_prepare_pg_leaves(srs_structure *S, double *compile_seconds, char *log, size_t log_cap);
+/* Developer hook, host only (needs no device): compiles a small row program in the emitted form, and a small two-gate ProtoGalaxy
+ * leaf unit, with hiprtc against the device
  * headers embedded in the library -- the run-time compilation path of srs_structure_create minus the module load.  0 and the
  * size of the gfx950 code object, or SRS_ERR_INVALID with the compiler log (log may be NULL).  A structure whose program fails to
  * compile silently stays on the interpreter, so this is the check that the path is alive. */

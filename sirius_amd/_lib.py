@@ -59,6 +59,7 @@ def _prototypes():
         "srs_glv_decompose": (i32, [i32, vp, i32, vp, vp, C.POINTER(i32), C.POINTER(i32)]),
         "srs_ck_shard_stats": (i32, [vp, i32, C.POINTER(C.c_uint64)]),
         "srs_structure_kernel_kind": (i32, [vp, i32]),
+        "srs_structure_prepare_pg_leaves": (i32, [vp, C.POINTER(C.c_double), C.c_char_p, sz]),
         "srs_ck_create": (i32, [i32, vp, sz, i32, C.POINTER(vp)]),
         "srs_ck_create_sharded": (i32, [i32, vp, sz, i32, u32, u32, C.POINTER(vp)]),
         "srs_ck_setup_synthetic": (i32, [i32, sz, C.c_uint64, u32, u32, C.POINTER(vp)]),

@@ -1901,6 +1901,25 @@ int srs_jit_selfcheck(size_t *code_bytes, char *log, size_t log_cap) {
     return ok ? SRS_OK : fail(SRS_ERR_INVALID, "srs_jit_selfcheck: hiprtc rejected the emitted form: " + text.substr(0, 400));
 }
 
+int srs_structure_prepare_pg_leaves(srs_structure *S, double *compile_seconds, char *log, size_t log_cap) {
+    if (log && log_cap) log[0] = 0;
+    if (compile_seconds) *compile_seconds = 0;
+    if (!S) return fail(SRS_ERR_INVALID, "srs_structure_prepare_pg_leaves: null structure");
+    if (int rc = ensure_device()) return rc;               // the module is loaded into the calling thread's device
+    return guarded([&]() -> int {
+        std::string text;
+        const int rc = rowprog::pg_jit_ensure(S->s, false, compile_seconds, text);
+        if (rc == 0) return SRS_OK;
+        if (rc == SRS_ERR_UNSUPPORTED) return fail(SRS_ERR_UNSUPPORTED, "srs_structure_prepare_pg_leaves: " + text);
+        if (log && log_cap) {
+            const size_t n = std::min(text.size(), log_cap - 1);
+            std::memcpy(log, text.data(), n);
+            log[n] = 0;
+        }
+        return fail(SRS_ERR_INVALID, "srs_structure_prepare_pg_leaves: the leaf kernels did not compile, the interpreter stays: " + text.substr(0, 400));
+    });
+}
+
 int srs_structure_kernel_kind(const srs_structure *S, int which) {
     if (!S || which < 0 || which > 2) return -1;
     return rowprog::kernel_kind(S->s, which);

@@ -95,8 +95,20 @@ int lincomb_rows(int field, fe_t *out, const fe_t *const *w_dev, const fe_t *coe
 // ahead-of-time kernel it maps to (-1: interpreter)
 const char *spec_source(Structure *S, int which, uint64_t *fingerprint, int *spec_id, std::string &buf);
 int kernel_kind(const Structure *S, int which);      // which: 0 cross terms, 1 gates, 2 ProtoGalaxy leaves -> 0 / 1 / 2
-// hiprtc compiles a small program in the emitted form against the embedded device headers (host only, no device needed)
+// hiprtc compiles a small program in the emitted form, and a small ProtoGalaxy leaf unit, against the embedded device headers (host
+// only, no device needed)
 bool jit_selfcheck(size_t *code_bytes, std::string &log);
+// The ProtoGalaxy leaf kernels of a gate set without ahead-of-time ones, compiled at run time: once per structure, on the first call that
+// runs leaves over the intended rows (`lazy`: only from 2^14 rows on, or tuning jit_always) or when asked (srs_structure_prepare_pg_leaves).
+// rc 0: the structure has compiled or ahead-of-time leaf kernels; 10: the rule excludes it (err says why); 4: the compile failed
+// (err = the compiler log), the structure stays on the interpreter.
+int pg_jit_ensure(Structure *S, bool lazy, double *compile_seconds, std::string &err);
+// TOOL-ONLY (not part of the engine's interface; nothing in the library calls them across units): the translation units themselves and
+// the size the cap is applied to, exported so that the host-only tools/pg_jit_compile_probe.cpp can time hiprtc on them without a device
+struct Compiled;
+std::string pg_leaf_unit_source(const Compiled &c, bool *sweep_form, int waves = 2);
+std::string cross_unit_source(const Compiled &c, int field);
+size_t pg_leaf_unit_insns(const Compiled &c);
 
 // lookup arguments (src/plonk/lookup.rs): all pointers DEVICE; ls / ts / ms HOST arrays of num_lookups DEVICE vectors
 int lookup_coeff_1(Structure *S, const fe_t *advice_dev, const fe_t &r, fe_t *const *ls, fe_t *const *ts, fe_t *const *ms,

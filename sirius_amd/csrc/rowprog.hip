@@ -121,52 +121,9 @@ __global__ void SRS_KERNEL_BOUNDS(RP_THREADS, 2) k_rowprog_spec(DevArgs A) {
 // evaluate_e: P = 1                                                   (protogalaxy/mod.rs:571-640)
 // The reference reduces with a binary tree where the right child is scaled by c_height; the same
 // tree is evaluated here level by level (LDS inside a workgroup, then across workgroups).
+// The argument blocks (GateProg, PgArgs, PgFLevels), the tile ownership, the weighted tree and the bodies of the specialised leaf
+// kernels are in rowprog_dev.cuh: the kernels compiled at run time for other gate sets (pg_leaf_unit_source) share them.
 // ---------------------------------------------------------------------------------------------
-struct GateProg {
-    const Insn *prog;
-    uint32_t n_insn, result, n_uniform, utab_off;   // utab_off: offset (in fe) of this gate's table in PgArgs.utab
-};
-struct PgArgs {
-    const GateProg *gates;
-    uint32_t n_gates, log_rows;
-    RowCtx ctx;
-    int compat;               // Q1: row_index = index & 2^k  ==> every leaf is evaluated at row 0
-    uint32_t leaf_pts;        // 1 (F, e) or P (G)
-    uint32_t P;
-    const fe_t *utab;         // per gate: [leaf_pts][n_uniform]
-    const fe_t *weights;      // [levels][wpts]
-    uint32_t wpts;            // P (F) or 1 (G, e)
-    uint32_t tile_log;        // leaves per workgroup = 2^tile_log (<= 7)
-    fe_t *partial;            // [n_gates * tiles_per_gate][P]
-    uint32_t shard_rank, shard_world;   // process-per-GPU runs (set_shard): a 1024-leaf tile IS a key stripe (STRIPE_LOG), this rank
-                              //   evaluates the tiles t % world == rank and leaves zeros for the others: its result is a PARTIAL sum
-    // reference leaf rows (compat): every leaf of a gate is that gate AT ROW 0 -- one value per (gate, point) for the whole launch.  r03 shared it
-    // among the 8 leaves of a thread; r04 hoists it out of the leaf pass: a one-workgroup launch (hoist_mode 1) evaluates the gates and leaves
-    // hoist[gate * P + p], the leaf launch (hoist_mode 2) reads it -- every leaf still enters the tree with its own weight.  0: evaluate per thread.
-    fe_t *hoist;
-    int hoist_mode;
-};
-__device__ __forceinline__ bool pg_tile_is_mine(const PgArgs &A, uint32_t tile) {
-    return A.shard_world <= 1 || tile % A.shard_world == A.shard_rank;
-}
-// a tile of another rank: zero partial sums (block-uniform exit before any barrier)
-__device__ __forceinline__ void pg_zero_partial(const PgArgs &A, uint32_t gate, uint32_t tile) {
-    for (uint32_t p = threadIdx.x; p < A.P; p += blockDim.x) A.partial[((size_t)gate * gridDim.x + tile) * A.P + p] = Fr::zero();
-}
-
-// binary-tree combine of blockDim.x values: v[2t] + v[2t+1] * w[level]; result in red[0]
-template <class F>
-__device__ __forceinline__ void weighted_tree(fe_t *red, fe_t x, const fe_t *__restrict__ w, uint32_t wstride, uint32_t levels) {
-    const uint32_t tid = threadIdx.x;
-    red[tid] = x;
-    __syncthreads();
-    for (uint32_t l = 0; l < levels; ++l) {
-        uint32_t stride = 1u << l;
-        if ((tid & (2 * stride - 1)) == 0) red[tid] = F::add(red[tid], F::mul(red[tid + stride], w[(size_t)l * wstride]));
-        __syncthreads();
-    }
-}
-
 // grid = (tiles_per_gate, n_gates), block = T = 2^(tile_log - log2 LPT) threads.  Thread t owns the LPT leaves
 // base + l * T + t (l < LPT): consecutive lanes read consecutive rows, so every column load is coalesced.  The sum
 // sum_i pow_i(c) f_i does not care about the order of additions (exact arithmetic), only that leaf i meets the weights
@@ -176,7 +133,7 @@ template <class F, uint32_t NSLOT, uint32_t LPT>
 __global__ void SRS_KERNEL_BOUNDS(RP_THREADS, 1) k_pg_leaves(PgArgs A) {
     __shared__ fe_t slots[NSLOT * RP_THREADS];
     __shared__ fe_t red[RP_THREADS];
-    constexpr uint32_t LPT_LOG = LPT == 8 ? 3 : (LPT == 4 ? 2 : (LPT == 2 ? 1 : 0));
+    constexpr uint32_t LPT_LOG = pg_lpt_log(LPT);
     const uint32_t gate = blockIdx.y, tile = blockIdx.x;
     const GateProg G = A.gates[gate];
     if (A.compat && A.hoist_mode == 1) {      // r06, as the ahead-of-time kernels: the reference's leaf rows make every leaf of a gate that gate AT ROW 0 --
@@ -185,7 +142,7 @@ __global__ void SRS_KERNEL_BOUNDS(RP_THREADS, 1) k_pg_leaves(PgArgs A) {
         if (threadIdx.x == 0) A.hoist[(size_t)gate * A.leaf_pts + tile] = x;
         return;
     }
-    if (!pg_tile_is_mine(A, tile)) { pg_zero_partial(A, gate, tile); return; }
+    if (!pg_tile_is_mine(A, tile)) { pg_zero_partial<F>(A, gate, tile); return; }
     const uint32_t TL = A.tile_log - LPT_LOG;                          // log2(blockDim.x)
     const uint32_t row0 = (tile << A.tile_log) + threadIdx.x;          // < rows (rows is a multiple of the tile)
     fe_t v[LPT];
@@ -219,90 +176,20 @@ __global__ void SRS_KERNEL_BOUNDS(RP_THREADS, 1) k_pg_leaves(PgArgs A) {
 }
 
 // k_pg_leaves with the gate programs of a known gate set compiled ahead of time (rowprog_spec.inc, PgSpecCall):
-// no LDS register file, no decode -- same leaf mapping and tree.
+// no LDS register file, no decode -- same leaf mapping and tree (pg_leaves_spec_body).
 template <class F, int ID, uint32_t LPT>
 __global__ void SRS_KERNEL_BOUNDS(RP_THREADS, 2) k_pg_leaves_spec(PgArgs A) {
     __shared__ fe_t red[RP_THREADS];
-    constexpr uint32_t LPT_LOG = LPT == 8 ? 3 : (LPT == 4 ? 2 : (LPT == 2 ? 1 : 0));
-    const uint32_t gate = blockIdx.y, tile = blockIdx.x;
-    if (!pg_tile_is_mine(A, tile)) { pg_zero_partial(A, gate, tile); return; }
-    const GateProg G = A.gates[gate];
-    const uint32_t TL = A.tile_log - LPT_LOG;
-    const uint32_t row0 = (tile << A.tile_log) + threadIdx.x;
-    fe_t v[LPT];
-    for (uint32_t p = 0; p < A.P; ++p) {
-        if (A.leaf_pts > 1 || p == 0) {
-#pragma unroll
-            for (uint32_t l = 0; l < LPT; ++l)
-                v[l] = PgSpecCall<F, ID>::run(gate, A.ctx, A.compat ? 0u : row0 + (l << TL), p,
-                                              A.utab + G.utab_off + (size_t)p * G.n_uniform);
-        }
-        const fe_t *w = A.weights + (A.wpts > 1 ? p : 0);
-        fe_t t[LPT];
-#pragma unroll
-        for (uint32_t l = 0; l < LPT; ++l) t[l] = v[l];
-#pragma unroll
-        for (uint32_t lvl = 0; lvl < LPT_LOG; ++lvl) {
-            fe_t c = w[(size_t)(TL + lvl) * A.wpts];
-#pragma unroll
-            for (uint32_t i = 0; i < (LPT >> (lvl + 1)); ++i) t[i] = F::add(t[2 * i], F::mul(t[2 * i + 1], c));
-        }
-        weighted_tree<F>(red, t[0], w, A.wpts, TL);
-        if (threadIdx.x == 0) A.partial[((size_t)gate * gridDim.x + tile) * A.P + p] = red[0];
-        __syncthreads();
-    }
+    pg_leaves_spec_body<F, PgSpecCall<F, ID>, LPT>(A, red);
 }
 
 // k_pg_leaves_spec in sweep form (compute_G with integer points, evaluate_e): every leaf row is swept ONCE for all P points
-// (its columns are read once, the Lagrange fold advances by one addition per point).  The thread's LPT leaves need the weights
-// w_l = prod_{b in bits(l)} c_(TL + b) of the leaf-index bits it owns: the host multiplies the term coefficients of the
-// uniform table by w_l (one table per l, A.utab = [gate][l][P][nu]), so leaf l simply ACCUMULATES onto the same lazy 9 x 29-bit
-// sums in LDS; between leaves the sums are folded below 2p.  Needs wpts == 1, P <= DMAX + 1 and affine advice leaves.
+// (pg_leaves_sweep_body)
 template <class F, int ID, uint32_t LPT, bool COMPAT>
 __global__ void SRS_KERNEL_BOUNDS(RP_THREADS, 2) k_pg_leaves_sweep(PgArgs A) {
     __shared__ fe_t red[RP_THREADS];
     SRS_SWEEP_ACC(acc_all);                                 // sweep_smem_bytes(P) of dynamic LDS
-    constexpr uint32_t LPT_LOG = LPT == 8 ? 3 : (LPT == 4 ? 2 : (LPT == 2 ? 1 : 0));
-    const uint32_t gate = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x;
-    if (!(COMPAT && A.hoist_mode == 1) && !pg_tile_is_mine(A, tile)) { pg_zero_partial(A, gate, tile); return; }
-    const GateProg G = A.gates[gate];
-    const uint32_t TL = A.tile_log - LPT_LOG;
-    const uint32_t row0 = (tile << A.tile_log) + tid;
-    uint32_t *acc = acc_all + tid;
-    const fe_t *U0 = A.utab + G.utab_off;
-    const fe_t one261 = U0[PgSpecCall<F, ID>::one(gate)];
-    if constexpr (COMPAT) {
-        // the reference's leaf rows (`index & 2^k`, src/plonk/mod.rs:714): the LPT leaves of a thread all sit at row 0 of this gate,
-        // so they share ONE gate evaluation f(X_p); sum_l w_l f = (sum_l w_l) f exactly -- table LPT holds the term coefficients
-        // times the sum of the thread's leaf weights (pg_sum).  The value is the same for every thread of every tile: hoisted (PgArgs::hoist)
-        if (A.hoist_mode == 2) {                                // the leaf launch: the hoisted values, then the trees
-            for (uint32_t p = 0; p < A.P; ++p) {
-                weighted_tree<F>(red, A.hoist[(size_t)gate * A.P + p], A.weights, A.wpts, TL);
-                if (tid == 0) A.partial[((size_t)gate * gridDim.x + tile) * A.P + p] = red[0];
-                __syncthreads();
-            }
-            return;
-        }
-        if (A.hoist_mode == 1) {                                // the hoisting launch, grid = (P, gates): workgroup p evaluates point p alone
-            RowCtx c = A.ctx;                                   // (the points are independent: P short chains side by side instead of one long one)
-            c.pt0 += tile;
-            PgSpecCall<F, ID>::sweep(gate, c, 0u, 1u, U0 + ((size_t)LPT * A.P + tile) * G.n_uniform, G.n_uniform, acc, false);
-            if (tid == 0) A.hoist[(size_t)gate * A.P + tile] = sw_finish<F>(acc, 0, one261);
-            return;
-        }
-        PgSpecCall<F, ID>::sweep(gate, A.ctx, 0u, A.P, U0 + (size_t)LPT * A.P * G.n_uniform, G.n_uniform, acc, false);
-    } else {
-        for (uint32_t l = 0; l < LPT; ++l) {
-            PgSpecCall<F, ID>::sweep(gate, A.ctx, row0 + (l << TL), A.P, U0 + (size_t)l * A.P * G.n_uniform, G.n_uniform, acc, l != 0);
-            if (l + 1 < LPT)
-                for (uint32_t p = 0; p < A.P; ++p) sw_fold<F>(acc, p, one261);
-        }
-    }
-    for (uint32_t p = 0; p < A.P; ++p) {
-        weighted_tree<F>(red, sw_finish<F>(acc, p, one261), A.weights, A.wpts, TL);
-        if (tid == 0) A.partial[((size_t)gate * gridDim.x + tile) * A.P + p] = red[0];
-        __syncthreads();
-    }
+    pg_leaves_sweep_body<F, PgSpecCall<F, ID>, LPT, COMPAT>(A, red, acc_all);
 }
 
 // compute_F as a POLYNOMIAL tree (no evaluation points, no ifft).  F(X) = sum_i f_i prod_{b in bits(i)} (beta_b + X delta_b)
@@ -312,65 +199,16 @@ __global__ void SRS_KERNEL_BOUNDS(RP_THREADS, 2) k_pg_leaves_sweep(PgArgs A) {
 // (exact arithmetic: identical coefficients, the ones above degree t are exactly zero in the reference's ifft too).
 // k_pg_F_leaves: every thread evaluates its 8 leaves (same coalesced mapping as k_pg_leaves) and folds them over the
 // three leaf-index bits it owns into a cubic; nodes are stored coefficient-major nodes[m * n_nodes + node].
-struct PgFLevels {
-    fe_t beta[3], delta[3];      // weights of leaf-index bits TL, TL + 1, TL + 2
-};
 template <class F, uint32_t NSLOT, int ID>
 __global__ void SRS_KERNEL_BOUNDS(RP_THREADS, 1) k_pg_F_leaves(PgArgs A, PgFLevels Lv, fe_t *__restrict__ nodes, uint32_t n_nodes) {
     __shared__ fe_t slots[NSLOT * RP_THREADS];
-    constexpr uint32_t LPT = 8, LPT_LOG = 3;
-    const uint32_t gate = blockIdx.y, tile = blockIdx.x;
-    if (!(A.compat && A.hoist_mode == 1) && !pg_tile_is_mine(A, tile)) {          // another rank's tile: zero cubic
-        const uint32_t node = (gate * gridDim.x + tile) * blockDim.x + threadIdx.x;
-        for (uint32_t m = 0; m < 4; ++m) nodes[(size_t)m * n_nodes + node] = F::zero();
-        return;
+    if constexpr (ID >= 0) {                               // the ahead-of-time gate set: sweep form with one point (NSLOT >= 2: 9 words per thread fit)
+        pg_F_leaves_body<F>(A, Lv, nodes, n_nodes, PgFLeafSweep<F, PgSpecCall<F, (ID >= 0 ? ID : 0)>>{reinterpret_cast<uint32_t *>(slots) + threadIdx.x});
+    } else {
+        pg_F_leaves_body<F>(A, Lv, nodes, n_nodes, [&](const PgArgs &a, const GateProg &G, uint32_t, uint32_t row) {
+            return interp<F>(slots, G.prog, G.n_insn, G.result, a.ctx, row, 0, a.utab + G.utab_off);
+        });
     }
-    const GateProg G = A.gates[gate];
-    const uint32_t TL = A.tile_log - LPT_LOG;
-    const uint32_t row0 = (tile << A.tile_log) + threadIdx.x;
-    fe_t v[LPT];
-#pragma unroll
-    for (uint32_t l = 0; l < LPT; ++l) {
-        if (A.compat && l) {                               // reference leaf rows (src/plonk/mod.rs:714): all LPT leaves are the gate at row 0
-            v[l] = v[0];
-            continue;
-        }
-        if (A.compat && A.hoist_mode == 2) {               // ... evaluated once per launch (PgArgs::hoist)
-            v[0] = A.hoist[gate];
-            continue;
-        }
-        const uint32_t row = A.compat ? 0u : row0 + (l << TL);
-        if constexpr (ID >= 0) {                           // sweep form with one point: the 9 x 29-bit multiplier
-            using PC = PgSpecCall<F, (ID >= 0 ? ID : 0)>;
-            uint32_t *acc = reinterpret_cast<uint32_t *>(slots) + threadIdx.x;      // NSLOT >= 2: 9 words per thread fit
-            PC::sweep(gate, A.ctx, row, 1, A.utab + G.utab_off, G.n_uniform, acc, false);
-            v[l] = sw_finish<F>(acc, 0, (A.utab + G.utab_off)[PC::one(gate)]);
-        } else {
-            v[l] = interp<F>(slots, G.prog, G.n_insn, G.result, A.ctx, row, 0, A.utab + G.utab_off);
-        }
-        if (A.compat && A.hoist_mode == 1) {               // the one-workgroup launch: the gate at row 0, nothing else
-            if (threadIdx.x == 0) A.hoist[gate] = v[0];
-            return;
-        }
-    }
-    fe_t c0[4], c1[4];                                     // bit TL: (v0 + v1 (beta + X delta))
-#pragma unroll
-    for (uint32_t j = 0; j < 4; ++j) {
-        c0[j] = F::add(v[2 * j], F::mul(v[2 * j + 1], Lv.beta[0]));
-        c1[j] = F::mul(v[2 * j + 1], Lv.delta[0]);
-    }
-    fe_t e0[2], e1[2], e2[2];                              // bit TL + 1
-#pragma unroll
-    for (uint32_t j = 0; j < 2; ++j) {
-        e0[j] = F::add(c0[2 * j], F::mul(c0[2 * j + 1], Lv.beta[1]));
-        e1[j] = F::add(F::add(c1[2 * j], F::mul(c1[2 * j + 1], Lv.beta[1])), F::mul(c0[2 * j + 1], Lv.delta[1]));
-        e2[j] = F::mul(c1[2 * j + 1], Lv.delta[1]);
-    }
-    const uint32_t node = (gate * gridDim.x + tile) * blockDim.x + threadIdx.x;      // bit TL + 2
-    nodes[(size_t)0 * n_nodes + node] = F::add(e0[0], F::mul(e0[1], Lv.beta[2]));
-    nodes[(size_t)1 * n_nodes + node] = F::add(F::add(e1[0], F::mul(e1[1], Lv.beta[2])), F::mul(e0[1], Lv.delta[2]));
-    nodes[(size_t)2 * n_nodes + node] = F::add(F::add(e2[0], F::mul(e2[1], Lv.beta[2])), F::mul(e1[1], Lv.delta[2]));
-    nodes[(size_t)3 * n_nodes + node] = F::mul(e2[1], Lv.delta[2]);
 }
 
 // one level of the polynomial tree: out[i] = in[2i] + in[2i+1] * (beta + X delta); nodes >= m_valid are zero.
@@ -820,6 +658,63 @@ static std::string jit_translation_unit(const std::string &fn_source, int field,
            ">(A, [](const RowCtx &C, uint32_t row, uint32_t pt, const fe_t *U) { return jit_fn<" + fname + ">(C, row, pt, U); });\n}\n}\n}\n";
 }
 
+// The translation unit of a gate set's ProtoGalaxy leaf kernels: `fn_sources` holds, per gate g, the emitted program pg_jit_fn_<g>
+// (emit_spec_source) and, with `sweep`, its sweep form pg_jit_fn_<g>_sweep (emit_sweep_source).  A dispatcher over the gate -- the
+// PgSpecCall of tools/gen_rowprog_spec.py, a switch on the wave-uniform gate index -- and extern "C" kernels over the bodies the
+// ahead-of-time kernels use (rowprog_dev.cuh): the leaves in `run` form, the leaves in sweep form (intended rows only: the reference's
+// rows of such a structure stay on the hoisted interpreter pass), and F's leaf cubics (sweep form with one point when there is one).
+static std::string pg_leaf_unit(const std::string &fn_sources, size_t n_gates, bool sweep, int waves) {
+    const std::string bounds = "__launch_bounds__(128, " + std::to_string(waves == 1 ? 1 : 2) + ")";
+    auto chain = [&](const std::string &ret, const std::string &suffix, const std::string &args) {
+        std::string o = "        switch (gate) {\n";
+        for (size_t g = 0; g + 1 < n_gates; ++g)
+            o += "        case " + std::to_string(g) + ": " + ret + "pg_jit_fn_" + std::to_string(g) + suffix + "<Fr>(" + args + ");" + (ret.empty() ? " return;" : "") + "\n";
+        return o + "        default: " + ret + "pg_jit_fn_" + std::to_string(n_gates - 1) + suffix + "<Fr>(" + args + ");\n        }\n";
+    };
+    std::string o = "#include \"rowprog_dev.cuh\"\nnamespace srs {\nnamespace rowprog {\n" + fn_sources + "struct PgJitCall {\n"
+                    "    static __device__ __forceinline__ fe_t run(uint32_t gate, const RowCtx &C, uint32_t row, uint32_t pt, const fe_t *U) {\n" +
+                    chain("return ", "", "C, row, pt, U") + "    }\n";
+    if (sweep)
+        o += "    static __device__ __forceinline__ void sweep(uint32_t gate, const RowCtx &C, uint32_t row, uint32_t npts, const fe_t *U, uint32_t nu, "
+             "uint32_t *acc, bool accumulate) {\n" + chain("", "_sweep", "C, row, npts, U, nu, acc, accumulate") + "    }\n"
+             "    static __device__ __forceinline__ uint32_t one(uint32_t gate) {\n" + chain("return ", "_sweep_one", "") + "    }\n";
+    o += "};\n"
+         "extern \"C\" __global__ void " + bounds + " srs_pg_jit_leaves_run(PgArgs A) {\n"
+         "    __shared__ fe_t red[RP_THREADS];\n    pg_leaves_spec_body<Fr, PgJitCall, 8>(A, red);\n}\n";
+    if (sweep)
+        o += "extern \"C\" __global__ void " + bounds + " srs_pg_jit_leaves_sweep(PgArgs A) {\n"
+             "    __shared__ fe_t red[RP_THREADS];\n    SRS_SWEEP_ACC(acc_all);\n    pg_leaves_sweep_body<Fr, PgJitCall, 8, false>(A, red, acc_all);\n}\n";
+    o += "extern \"C\" __global__ void __launch_bounds__(128, 1) srs_pg_jit_F_leaves(PgFArgs B) {\n";
+    if (sweep)
+        o += "    __shared__ uint32_t acc[SW_WORDS * RP_THREADS];\n"
+             "    pg_F_leaves_body<Fr>(B.A, B.Lv, B.nodes, B.n_nodes, PgFLeafSweep<Fr, PgJitCall>{acc + threadIdx.x});\n";
+    else
+        o += "    pg_F_leaves_body<Fr>(B.A, B.Lv, B.nodes, B.n_nodes, PgFLeafRun<Fr, PgJitCall>{});\n";
+    return o + "}\n}\n}\n";
+}
+
+// ... of a structure's gate programs.  Only when EVERY gate has a sweep form does the unit carry the sweep-form kernels.
+std::string pg_leaf_unit_source(const Compiled &c, bool *sweep_form, int waves) {
+    bool sweep = !c.gate_progs.empty();
+    for (const Program &gp : c.gate_progs) sweep = sweep && gp.sweep_ok;
+    std::string fns;
+    for (size_t g = 0; g < c.gate_progs.size(); ++g) {
+        const std::string name = "pg_jit_fn_" + std::to_string(g);
+        fns += emit_spec_source(c.gate_progs[g], name, true);
+        if (sweep) fns += emit_sweep_source(c.gate_progs[g], name + "_sweep", true);
+    }
+    if (sweep_form) *sweep_form = sweep;
+    return pg_leaf_unit(fns, c.gate_progs.size(), sweep, waves);
+}
+std::string cross_unit_source(const Compiled &c, int field) {
+    return jit_translation_unit(emit_spec_source(c.cross, "jit_fn", true) + emit_sweep_source(c.cross, "jit_fn_sweep", true), field, c.cross.sweep_ok);
+}
+size_t pg_leaf_unit_insns(const Compiled &c) {
+    size_t n = 0;
+    for (const Program &gp : c.gate_progs) n += gp.vins.size();
+    return n;
+}
+
 // Host-only check of the run-time compilation path (no device): a small program in the emitted form -- column loads,
 // called and inlined multipliers, a uniform -- must compile with hiprtc against the headers embedded in the library.
 bool jit_selfcheck(size_t *code_bytes, std::string &log) {
@@ -854,6 +749,16 @@ bool jit_selfcheck(size_t *code_bytes, std::string &log) {
         if (!jit::compile_only(jit_translation_unit(fn, field, true), &bytes, log)) return false;
         if (code_bytes) *code_bytes = bytes;
     }
+    // ... and the ProtoGalaxy leaf unit (pg_leaf_unit: dispatcher and the three kernels over the bodies of rowprog_dev.cuh) of a canned
+    // two-gate set made of the same program, with the sweep form and without
+    auto renamed = [&](const std::string &to) {
+        std::string t = fn;
+        for (size_t at = 0; (at = t.find("jit_fn", at)) != std::string::npos; at += to.size()) t.replace(at, 6, to);
+        return t;
+    };
+    const std::string two = renamed("pg_jit_fn_0") + renamed("pg_jit_fn_1");
+    for (int sweep = 1; sweep >= 0; --sweep)
+        if (!jit::compile_only(pg_leaf_unit(two, 2, sweep != 0, 1 + sweep), nullptr, log)) return false;
     return true;
 }
 
@@ -865,6 +770,11 @@ struct Structure : Compiled {     // Compiled (rowprog_compile.h): the programs,
     bool has_vector_lookup = false;
     int pg_spec_id = -1;           // ahead-of-time specialised leaf kernel for this gate set, or -1
     GateProg *d_gate_progs = nullptr;
+    // the leaf kernels of this gate set compiled at run time (pg_jit_ensure): one module, pg_jit_run owns it; pg_jit_sweep only when every
+    // gate has a sweep form.  pg_jit_state: 0 not tried, 1 loaded, -1 the compile or the load failed (pg_jit_log; the interpreter stays)
+    jit::Kernel pg_jit_run, pg_jit_sweep, pg_jit_F;
+    int pg_jit_state = 0;
+    std::string pg_jit_log;
     // device data
     uint8_t **d_sel_ptrs = nullptr;
     fe_t **d_fix_ptrs = nullptr;
@@ -972,6 +882,9 @@ Structure *create(int field, uint32_t k, size_t num_selectors, size_t num_fixed,
 void destroy(Structure *S) {
     if (!S) return;
     jit::release(S->cross.jit);
+    jit::release(S->pg_jit_sweep);
+    jit::release(S->pg_jit_F);
+    jit::release(S->pg_jit_run);          // the module of all three
     for (void *p : S->owned) (void)hipFree(p);
     S->arena.release();
     S->lookup_scratch.release();
@@ -1008,8 +921,76 @@ static void launch_rowprog(const DevArgs &A, uint32_t nslots, hipStream_t st) {
 }
 
 // 0 interpreter, 1 ahead-of-time specialised kernel, 2 compiled at run time (include/sirius_amd.h SRS_KERNEL_*)
+// ---- ProtoGalaxy leaf kernels compiled at run time
+// The leaf kernels a call takes: 1 ahead of time, 2 compiled at run time, 0 interpreter.  The compiled ones serve the intended leaf rows
+// only (compat == 0): the reference's rows make every leaf of a gate one value, which the hoisted interpreter pass evaluates once.
+static int pg_leaf_kind(const Structure *S, int compat) {
+    if (!compat && S->pg_jit_run.function && (S->pg_spec_id < 0 || tuning::get_or(tuning::PG_JIT_FORCE, 0) != 0)) return 2;
+    return S->pg_spec_id >= 0 ? 1 : 0;
+}
+// ... and whether they include the sweep form (integer-point G, e, F's leaves)
+static bool pg_leaf_sweep_form(const Structure *S, int compat) {
+    const int kind = pg_leaf_kind(S, compat);
+    return kind == 1 || (kind == 2 && S->pg_jit_sweep.function != nullptr);
+}
+// A leaf unit inlines every gate program 8 times per kernel (the 8 leaves of a thread); hiprtc's time grows linearly with the summed SSA
+// instruction count of the gates, 1.4 - 2.1 times that of a cross-term unit of the same size (profiles/pg_leaves_jit_ab.txt).  The cap
+// is the size of the largest cross-term unit the library compiles at creation (degree 8: 4 x MainGate<5>, 313 instructions): a leaf
+// unit never takes more than about twice that one; above it the structure stays on the interpreter.
+constexpr size_t PG_JIT_MAX_INSNS = 320;
+// The two leaf kernels of a unit are bounded for two waves per SIMD (256 VGPRs), as the ahead-of-time ones; a unit of more than
+// PG_JIT_ONE_WAVE_INSNS instructions for one (512): large gate programs spill at 256 (profiles/pg_leaves_jit_ab.txt).  Tuning
+// pg_jit_waves overrides the choice.
+constexpr size_t PG_JIT_ONE_WAVE_INSNS = PG_JIT_MAX_INSNS;      // no unit below the cap measured faster at one wave
+static int pg_jit_waves(const Structure *S) {
+    const int64_t t = tuning::get_or(tuning::PG_JIT_WAVES, 0);
+    if (t == 1 || t == 2) return (int)t;
+    return pg_leaf_unit_insns(*S) > PG_JIT_ONE_WAVE_INSNS ? 1 : 2;
+}
+// Whether the structure may get compiled leaf kernels; `lazy`: asked by a call that is about to run leaves over rows (then only
+// from 2^14 rows on, the rule of the cross terms), else by srs_structure_prepare_pg_leaves.
+static bool pg_jit_allowed(const Structure *S, bool lazy, std::string &why) {
+    if (S->field != 0) { why = "ProtoGalaxy leaves exist for bn256::Fr only"; return false; }
+    if (S->gate_progs.empty()) { why = "the structure has no gates"; return false; }
+    if (S->k < 10) { why = "fewer than 2^10 rows: the leaf kernels map 8 leaves to a thread from 2^10 rows on"; return false; }
+    if (!jit::enabled()) { why = "run-time compilation is disabled (tuning no_jit / SRS_NO_JIT)"; return false; }
+    if (lazy && S->k < 14 && tuning::get_or(tuning::JIT_ALWAYS, 0) == 0) { why = "fewer than 2^14 rows"; return false; }
+    const size_t insns = pg_leaf_unit_insns(*S);
+    if (insns > PG_JIT_MAX_INSNS) {
+        why = "the gate programs have " + std::to_string(insns) + " instructions, more than the " + std::to_string(PG_JIT_MAX_INSNS) +
+              " a leaf unit is compiled for: the leaves stay on the interpreter";
+        return false;
+    }
+    return true;
+}
+// Compiles and loads the leaf unit once per structure.  rc 0: compiled (now or earlier) or ahead-of-time kernels; 10: the rule excludes
+// the structure (err says why); 4: the compile failed (err = the compiler's log; the structure stays on the interpreter).
+int pg_jit_ensure(Structure *S, bool lazy, double *compile_seconds, std::string &err) {
+    if (compile_seconds) *compile_seconds = 0;
+    if (S->pg_spec_id >= 0 && tuning::get_or(tuning::PG_JIT_FORCE, 0) == 0) return 0;
+    if (S->pg_jit_state > 0) return 0;
+    if (S->pg_jit_state < 0) { err = S->pg_jit_log; return 4; }
+    if (!pg_jit_allowed(S, lazy, err)) return 10;
+    bool sweep = false;
+    const std::string src = pg_leaf_unit_source(*S, &sweep, pg_jit_waves(S));
+    std::string log;
+    bool ok = jit::compile_unit(src, "srs_pg_jit_leaves_run", S->pg_jit_run, log) && jit::entry(S->pg_jit_run, "srs_pg_jit_F_leaves", S->pg_jit_F, log) &&
+              (!sweep || jit::entry(S->pg_jit_run, "srs_pg_jit_leaves_sweep", S->pg_jit_sweep, log));
+    if (compile_seconds) *compile_seconds = S->pg_jit_run.compile_seconds;
+    if (!ok) {
+        jit::release(S->pg_jit_sweep);
+        jit::release(S->pg_jit_F);
+        jit::release(S->pg_jit_run);
+        S->pg_jit_state = -1;
+        S->pg_jit_log = err = log.empty() ? "run-time compilation of the leaf kernels failed" : log;
+        return 4;
+    }
+    S->pg_jit_state = 1;
+    return 0;
+}
+
 int kernel_kind(const Structure *S, int which) {
-    if (which == 2) return S->pg_spec_id >= 0 ? 1 : 0;
+    if (which == 2) return pg_leaf_kind(S, 0);
     const Program &p = which == 0 ? S->cross : S->plain_compressed;
     if (p.spec_id >= 0) return 1;
     if (p.jit.function) return 2;
@@ -1369,7 +1350,12 @@ static PgArgs pg_args(const Structure *S, const fe_t *const *W_dev, const GatePr
 // one leaf launch: the ahead-of-time gate set (8 leaves per thread only; sweep: its sweep form), else the interpreter by live registers
 static void launch_leaves(const Structure *S, const PgArgs &a, uint32_t tiles, uint32_t threads, uint32_t lpt, uint32_t max_slots, bool sweep,
                           hipStream_t st) {
-    if (S->pg_spec_id >= 0 && lpt == PG_LPT) launch_pg_spec(S->pg_spec_id, a, tiles, a.n_gates, threads, st, sweep);
+    const int kind = lpt == PG_LPT ? pg_leaf_kind(S, a.compat) : 0;
+    if (kind == 2) {
+        if (!jit::launch_grid(sweep ? S->pg_jit_sweep : S->pg_jit_run, tiles, a.n_gates, threads, sweep ? sweep_smem_bytes(a.P) : 0u, &a, st))
+        { set_error("launch of the run-time compiled ProtoGalaxy leaf kernel failed"); throw DeviceError{5}; }
+    }
+    else if (kind == 1) launch_pg_spec(S->pg_spec_id, a, tiles, a.n_gates, threads, st, sweep);
     else if (max_slots <= 8) launch_pg_leaves<8>(a, tiles, a.n_gates, threads, lpt, st);
     else if (max_slots <= 12) launch_pg_leaves<12>(a, tiles, a.n_gates, threads, lpt, st);
     else if (max_slots <= 16) launch_pg_leaves<16>(a, tiles, a.n_gates, threads, lpt, st);
@@ -1378,7 +1364,11 @@ static void launch_leaves(const Structure *S, const PgArgs &a, uint32_t tiles, u
 
 static void launch_F_leaves(const Structure *S, const PgArgs &a, const PgFLevels &lv, uint32_t tiles, uint32_t threads, uint32_t max_slots, fe_t *out,
                             uint32_t n0, hipStream_t st) {
-    if (S->pg_spec_id == 0) SRS_LAUNCH((k_pg_F_leaves<Fr, 2, 0>), (tiles, a.n_gates), (threads), 0, st, a, lv, out, n0);
+    if (pg_leaf_kind(S, a.compat) == 2) {
+        const PgFArgs fa{a, lv, out, n0};
+        if (!jit::launch_grid(S->pg_jit_F, tiles, a.n_gates, threads, 0u, &fa, st)) { set_error("launch of the run-time compiled ProtoGalaxy F leaf kernel failed"); throw DeviceError{5}; }
+    }
+    else if (S->pg_spec_id == 0) SRS_LAUNCH((k_pg_F_leaves<Fr, 2, 0>), (tiles, a.n_gates), (threads), 0, st, a, lv, out, n0);
     else if (max_slots <= 8) SRS_LAUNCH((k_pg_F_leaves<Fr, 8, -1>), (tiles, a.n_gates), (threads), 0, st, a, lv, out, n0);
     else if (max_slots <= 16) SRS_LAUNCH((k_pg_F_leaves<Fr, 16, -1>), (tiles, a.n_gates), (threads), 0, st, a, lv, out, n0);
     else SRS_LAUNCH((k_pg_F_leaves<Fr, 32, -1>), (tiles, a.n_gates), (threads), 0, st, a, lv, out, n0);
@@ -1686,8 +1676,8 @@ static int pg_leaf_sums(Structure *S, int mode, const fe_t *const *W_dev, const 
     // weights are betas_stroke = beta + alpha delta^(2^b), so G(1) = sum_i pow_i(betas_stroke) f_i(acc) = F(alpha) -- an
     // identity of the definitions, whatever the traces hold.  ProtoGalaxy::prove has F(alpha) (it is compute_K's first
     // argument): with `g_at_one` the leaves are evaluated at X = 2 .. d_G + 1 only (d_G points), and the interpolation
-    // nodes are 1 .. d_G + 1.  Needs the sweep-form leaf kernel (below); otherwise all d_G + 1 points are evaluated.
-    const bool skip_one = g_int && g_at_one != nullptr && dG >= 2 && S->pg_spec_id >= 0 && lpt == PG_LPT && dG + 1 <= DMAX + 1;
+    // nodes are 1 .. d_G + 1.  Needs a sweep-form leaf kernel (below; ahead of time or compiled); otherwise all d_G + 1 points are evaluated.
+    const bool skip_one = g_int && g_at_one != nullptr && dG >= 2 && pg_leaf_sweep_form(S, compat) && lpt == PG_LPT && dG + 1 <= DMAX + 1;
     const uint32_t pt0 = skip_one ? 2u : 0u;
     const uint32_t P = g_int ? (skip_one ? dG : dG + 1) : P_out;   // evaluation points actually used
     const uint32_t leaf_pts = mode == 1 ? P : 1u;
@@ -1702,8 +1692,8 @@ static int pg_leaf_sums(Structure *S, int mode, const fe_t *const *W_dev, const 
         for (uint32_t b = 0; b < levels; ++b)
             for (uint32_t p = 0; p < P; ++p) weights[(size_t)b * P + p] = Fr::add(weights_in[b], Fr::mul(pp.pts[p], deltas[b]));
     }
-    // the specialised leaf kernel in sweep form (k_pg_leaves_sweep): integer-point G and evaluate_e of a known gate set
-    const bool sweep_leaves = S->pg_spec_id >= 0 && lpt == PG_LPT && mode != 0 && (mode != 1 || g_int) && P <= DMAX + 1;
+    // the specialised leaf kernel in sweep form (k_pg_leaves_sweep, or its run-time compiled twin): integer-point G and evaluate_e
+    const bool sweep_leaves = pg_leaf_sweep_form(S, compat) && lpt == PG_LPT && mode != 0 && (mode != 1 || g_int) && P <= DMAX + 1;
     PgSlotWeights sw;
     if (sweep_leaves) sw = pg_slot_weights_leaves(weights.data() + (tile_log - 3));      // (wpts == 1 in sweep form)
     PgGateTable t;
@@ -1792,6 +1782,9 @@ int pg_sum(Structure *S, int mode, const fe_t *const *W_dev, const fe_t *const *
         *n_out = P_out;
         return pg_closed(S, mode, W_dev, challenges_host, n_ch, J, weights_in, delta, (uint32_t)sz.betas_count, st, out_host, P_out, err);
     }
+    // leaves over rows from here on.  The intended rows of a gate set without ahead-of-time kernels: compile its leaf kernels on the first
+    // such call (never at creation: the reference's rows above pay nothing); whatever excludes it or fails leaves the interpreter in place
+    if (!compat) { std::string why; (void)pg_jit_ensure(S, true, nullptr, why); }
     // the evaluate-and-interpolate route of compute_F stays for small tables and as the cross-check (tuning pg_f_eval = 1)
     if (mode == 0 && S->k >= 10 && tuning::get_or(tuning::PG_F_EVAL, 0) == 0) {
         *n_out = P_out;

@@ -218,5 +218,223 @@ __device__ __forceinline__ void sweep_kernel_body(const DevArgs &A, uint32_t one
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// ProtoGalaxy leaves (rowprog.hip: "ProtoGalaxy: pow-weighted sums of gate evaluations").  The argument blocks and the kernel bodies
+// live here so that the ahead-of-time kernels (rowprog.hip, gate-set functor PgSpecCall<F, ID> of rowprog_spec.inc) and the kernels
+// compiled at run time for any other gate set (pg_leaf_unit_source) are the SAME code.  A gate-set functor PC has
+//   PC::run(gate, C, row, pt, U) -> fe_t          the straight-line program of `gate` at one point
+//   PC::sweep(gate, C, row, npts, U, nu, acc, accumulate)      its sweep form, all points per column load
+//   PC::one(gate)                                 index of 2^261 mod p in that gate's uniform table
+// ---------------------------------------------------------------------------------------------
+struct GateProg {
+    const Insn *prog;
+    uint32_t n_insn, result, n_uniform, utab_off;   // utab_off: offset (in fe) of this gate's table in PgArgs.utab
+};
+struct PgArgs {
+    const GateProg *gates;
+    uint32_t n_gates, log_rows;
+    RowCtx ctx;
+    int compat;               // Q1: row_index = index & 2^k  ==> every leaf is evaluated at row 0
+    uint32_t leaf_pts;        // 1 (F, e) or P (G)
+    uint32_t P;
+    const fe_t *utab;         // per gate: [leaf_pts][n_uniform]
+    const fe_t *weights;      // [levels][wpts]
+    uint32_t wpts;            // P (F) or 1 (G, e)
+    uint32_t tile_log;        // leaves per workgroup = 2^tile_log (<= 7)
+    fe_t *partial;            // [n_gates * tiles_per_gate][P]
+    uint32_t shard_rank, shard_world;   // process-per-GPU runs (set_shard): a 1024-leaf tile IS a key stripe (STRIPE_LOG), this rank
+                              //   evaluates the tiles t % world == rank and leaves zeros for the others: its result is a PARTIAL sum
+    // reference leaf rows (compat): every leaf of a gate is that gate AT ROW 0 -- one value per (gate, point) for the whole launch.  r03 shared it
+    // among the 8 leaves of a thread; r04 hoists it out of the leaf pass: a one-workgroup launch (hoist_mode 1) evaluates the gates and leaves
+    // hoist[gate * P + p], the leaf launch (hoist_mode 2) reads it -- every leaf still enters the tree with its own weight.  0: evaluate per thread.
+    fe_t *hoist;
+    int hoist_mode;
+};
+__device__ __forceinline__ bool pg_tile_is_mine(const PgArgs &A, uint32_t tile) {
+    return A.shard_world <= 1 || tile % A.shard_world == A.shard_rank;
+}
+// a tile of another rank: zero partial sums (block-uniform exit before any barrier)
+template <class F>
+__device__ __forceinline__ void pg_zero_partial(const PgArgs &A, uint32_t gate, uint32_t tile) {
+    for (uint32_t p = threadIdx.x; p < A.P; p += blockDim.x) A.partial[((size_t)gate * gridDim.x + tile) * A.P + p] = F::zero();
+}
+
+// binary-tree combine of blockDim.x values: v[2t] + v[2t+1] * w[level]; result in red[0]
+template <class F>
+__device__ __forceinline__ void weighted_tree(fe_t *red, fe_t x, const fe_t *__restrict__ w, uint32_t wstride, uint32_t levels) {
+    const uint32_t tid = threadIdx.x;
+    red[tid] = x;
+    __syncthreads();
+    for (uint32_t l = 0; l < levels; ++l) {
+        uint32_t stride = 1u << l;
+        if ((tid & (2 * stride - 1)) == 0) red[tid] = F::add(red[tid], F::mul(red[tid + stride], w[(size_t)l * wstride]));
+        __syncthreads();
+    }
+}
+
+SRS_HD constexpr uint32_t pg_lpt_log(uint32_t lpt) { return lpt == 8 ? 3 : (lpt == 4 ? 2 : (lpt == 2 ? 1 : 0)); }
+
+// Body of k_pg_leaves_spec: the leaf mapping and tree of k_pg_leaves (rowprog.hip) with the gate programs as straight-line code:
+// no LDS register file, no decode.  `red`: RP_THREADS elements of LDS.
+template <class F, class PC, uint32_t LPT>
+__device__ __forceinline__ void pg_leaves_spec_body(const PgArgs &A, fe_t *red) {
+    constexpr uint32_t LPT_LOG = pg_lpt_log(LPT);
+    const uint32_t gate = blockIdx.y, tile = blockIdx.x;
+    if (!pg_tile_is_mine(A, tile)) { pg_zero_partial<F>(A, gate, tile); return; }
+    const GateProg G = A.gates[gate];
+    const uint32_t TL = A.tile_log - LPT_LOG;
+    const uint32_t row0 = (tile << A.tile_log) + threadIdx.x;
+    fe_t v[LPT];
+    for (uint32_t p = 0; p < A.P; ++p) {
+        if (A.leaf_pts > 1 || p == 0) {
+#pragma unroll
+            for (uint32_t l = 0; l < LPT; ++l)
+                v[l] = PC::run(gate, A.ctx, A.compat ? 0u : row0 + (l << TL), p, A.utab + G.utab_off + (size_t)p * G.n_uniform);
+        }
+        const fe_t *w = A.weights + (A.wpts > 1 ? p : 0);
+        fe_t t[LPT];
+#pragma unroll
+        for (uint32_t l = 0; l < LPT; ++l) t[l] = v[l];
+#pragma unroll
+        for (uint32_t lvl = 0; lvl < LPT_LOG; ++lvl) {
+            fe_t c = w[(size_t)(TL + lvl) * A.wpts];
+#pragma unroll
+            for (uint32_t i = 0; i < (LPT >> (lvl + 1)); ++i) t[i] = F::add(t[2 * i], F::mul(t[2 * i + 1], c));
+        }
+        weighted_tree<F>(red, t[0], w, A.wpts, TL);
+        if (threadIdx.x == 0) A.partial[((size_t)gate * gridDim.x + tile) * A.P + p] = red[0];
+        __syncthreads();
+    }
+}
+
+// Body of k_pg_leaves_sweep, the sweep form (compute_G with integer points, evaluate_e): every leaf row is swept ONCE for all P points
+// (its columns are read once, the Lagrange fold advances by one addition per point).  The thread's LPT leaves need the weights
+// w_l = prod_{b in bits(l)} c_(TL + b) of the leaf-index bits it owns: the host multiplies the term coefficients of the
+// uniform table by w_l (one table per l, A.utab = [gate][l][P][nu]), so leaf l simply ACCUMULATES onto the same lazy 9 x 29-bit
+// sums in LDS; between leaves the sums are folded below 2p.  Needs wpts == 1, P <= DMAX + 1 and affine advice leaves.
+// `red`: RP_THREADS elements of LDS; `acc_all`: sweep_smem_bytes(P) of (dynamic) LDS.
+template <class F, class PC, uint32_t LPT, bool COMPAT>
+__device__ __forceinline__ void pg_leaves_sweep_body(const PgArgs &A, fe_t *red, uint32_t *acc_all) {
+    constexpr uint32_t LPT_LOG = pg_lpt_log(LPT);
+    const uint32_t gate = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x;
+    if (!(COMPAT && A.hoist_mode == 1) && !pg_tile_is_mine(A, tile)) { pg_zero_partial<F>(A, gate, tile); return; }
+    const GateProg G = A.gates[gate];
+    const uint32_t TL = A.tile_log - LPT_LOG;
+    const uint32_t row0 = (tile << A.tile_log) + tid;
+    uint32_t *acc = acc_all + tid;
+    const fe_t *U0 = A.utab + G.utab_off;
+    const fe_t one261 = U0[PC::one(gate)];
+    if constexpr (COMPAT) {
+        // the reference's leaf rows (`index & 2^k`, src/plonk/mod.rs:714): the LPT leaves of a thread all sit at row 0 of this gate,
+        // so they share ONE gate evaluation f(X_p); sum_l w_l f = (sum_l w_l) f exactly -- table LPT holds the term coefficients
+        // times the sum of the thread's leaf weights (pg_sum).  The value is the same for every thread of every tile: hoisted (PgArgs::hoist)
+        if (A.hoist_mode == 2) {                                // the leaf launch: the hoisted values, then the trees
+            for (uint32_t p = 0; p < A.P; ++p) {
+                weighted_tree<F>(red, A.hoist[(size_t)gate * A.P + p], A.weights, A.wpts, TL);
+                if (tid == 0) A.partial[((size_t)gate * gridDim.x + tile) * A.P + p] = red[0];
+                __syncthreads();
+            }
+            return;
+        }
+        if (A.hoist_mode == 1) {                                // the hoisting launch, grid = (P, gates): workgroup p evaluates point p alone
+            RowCtx c = A.ctx;                                   // (the points are independent: P short chains side by side instead of one long one)
+            c.pt0 += tile;
+            PC::sweep(gate, c, 0u, 1u, U0 + ((size_t)LPT * A.P + tile) * G.n_uniform, G.n_uniform, acc, false);
+            if (tid == 0) A.hoist[(size_t)gate * A.P + tile] = sw_finish<F>(acc, 0, one261);
+            return;
+        }
+        PC::sweep(gate, A.ctx, 0u, A.P, U0 + (size_t)LPT * A.P * G.n_uniform, G.n_uniform, acc, false);
+    } else {
+        for (uint32_t l = 0; l < LPT; ++l) {
+            PC::sweep(gate, A.ctx, row0 + (l << TL), A.P, U0 + (size_t)l * A.P * G.n_uniform, G.n_uniform, acc, l != 0);
+            if (l + 1 < LPT)
+                for (uint32_t p = 0; p < A.P; ++p) sw_fold<F>(acc, p, one261);
+        }
+    }
+    for (uint32_t p = 0; p < A.P; ++p) {
+        weighted_tree<F>(red, sw_finish<F>(acc, p, one261), A.weights, A.wpts, TL);
+        if (tid == 0) A.partial[((size_t)gate * gridDim.x + tile) * A.P + p] = red[0];
+        __syncthreads();
+    }
+}
+
+// compute_F as a POLYNOMIAL tree (rowprog.hip, k_pg_F_leaves): the weights of the three leaf-index bits a thread folds, and the
+// argument block of the run-time compiled kernel (one struct by value: jit::launch)
+struct PgFLevels {
+    fe_t beta[3], delta[3];      // weights of leaf-index bits TL, TL + 1, TL + 2
+};
+struct PgFArgs {
+    PgArgs A;
+    PgFLevels Lv;
+    fe_t *nodes;
+    uint32_t n_nodes;
+};
+// one leaf of F through a gate-set functor: the sweep form with one point (the 9 x 29-bit multiplier; `acc`: SW_WORDS words per thread
+// of LDS, limb-planar, already offset by the thread index), or the straight-line program
+template <class F, class PC>
+struct PgFLeafSweep {
+    uint32_t *acc;
+    __device__ __forceinline__ fe_t operator()(const PgArgs &A, const GateProg &G, uint32_t gate, uint32_t row) const {
+        PC::sweep(gate, A.ctx, row, 1, A.utab + G.utab_off, G.n_uniform, acc, false);
+        return sw_finish<F>(acc, 0, (A.utab + G.utab_off)[PC::one(gate)]);
+    }
+};
+template <class F, class PC>
+struct PgFLeafRun {
+    __device__ __forceinline__ fe_t operator()(const PgArgs &A, const GateProg &G, uint32_t gate, uint32_t row) const {
+        return PC::run(gate, A.ctx, row, 0, A.utab + G.utab_off);
+    }
+};
+// Body of k_pg_F_leaves: every thread evaluates its 8 leaves (`leaf(A, G, gate, row)`; same coalesced mapping as the leaf kernels above)
+// and folds them over the three leaf-index bits it owns into a cubic; nodes are stored coefficient-major nodes[m * n_nodes + node].
+template <class F, class Leaf>
+__device__ __forceinline__ void pg_F_leaves_body(const PgArgs &A, const PgFLevels &Lv, fe_t *__restrict__ nodes, uint32_t n_nodes, Leaf leaf) {
+    constexpr uint32_t LPT = 8, LPT_LOG = 3;
+    const uint32_t gate = blockIdx.y, tile = blockIdx.x;
+    if (!(A.compat && A.hoist_mode == 1) && !pg_tile_is_mine(A, tile)) {          // another rank's tile: zero cubic
+        const uint32_t node = (gate * gridDim.x + tile) * blockDim.x + threadIdx.x;
+        for (uint32_t m = 0; m < 4; ++m) nodes[(size_t)m * n_nodes + node] = F::zero();
+        return;
+    }
+    const GateProg G = A.gates[gate];
+    const uint32_t TL = A.tile_log - LPT_LOG;
+    const uint32_t row0 = (tile << A.tile_log) + threadIdx.x;
+    fe_t v[LPT];
+#pragma unroll
+    for (uint32_t l = 0; l < LPT; ++l) {
+        if (A.compat && l) {                               // reference leaf rows (src/plonk/mod.rs:714): all LPT leaves are the gate at row 0
+            v[l] = v[0];
+            continue;
+        }
+        if (A.compat && A.hoist_mode == 2) {               // ... evaluated once per launch (PgArgs::hoist)
+            v[0] = A.hoist[gate];
+            continue;
+        }
+        v[l] = leaf(A, G, gate, A.compat ? 0u : row0 + (l << TL));
+        if (A.compat && A.hoist_mode == 1) {               // the one-workgroup launch: the gate at row 0, nothing else
+            if (threadIdx.x == 0) A.hoist[gate] = v[0];
+            return;
+        }
+    }
+    fe_t c0[4], c1[4];                                     // bit TL: (v0 + v1 (beta + X delta))
+#pragma unroll
+    for (uint32_t j = 0; j < 4; ++j) {
+        c0[j] = F::add(v[2 * j], F::mul(v[2 * j + 1], Lv.beta[0]));
+        c1[j] = F::mul(v[2 * j + 1], Lv.delta[0]);
+    }
+    fe_t e0[2], e1[2], e2[2];                              // bit TL + 1
+#pragma unroll
+    for (uint32_t j = 0; j < 2; ++j) {
+        e0[j] = F::add(c0[2 * j], F::mul(c0[2 * j + 1], Lv.beta[1]));
+        e1[j] = F::add(F::add(c1[2 * j], F::mul(c1[2 * j + 1], Lv.beta[1])), F::mul(c0[2 * j + 1], Lv.delta[1]));
+        e2[j] = F::mul(c1[2 * j + 1], Lv.delta[1]);
+    }
+    const uint32_t node = (gate * gridDim.x + tile) * blockDim.x + threadIdx.x;      // bit TL + 2
+    nodes[(size_t)0 * n_nodes + node] = F::add(e0[0], F::mul(e0[1], Lv.beta[2]));
+    nodes[(size_t)1 * n_nodes + node] = F::add(F::add(e1[0], F::mul(e1[1], Lv.beta[2])), F::mul(e0[1], Lv.delta[2]));
+    nodes[(size_t)2 * n_nodes + node] = F::add(F::add(e2[0], F::mul(e2[1], Lv.beta[2])), F::mul(e1[1], Lv.delta[2]));
+    nodes[(size_t)3 * n_nodes + node] = F::mul(e2[1], Lv.delta[2]);
+}
+
 }  // namespace rowprog
 }  // namespace srs

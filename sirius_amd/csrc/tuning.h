@@ -27,6 +27,8 @@ enum Id : int {
     NO_JIT,             // 1: never call hiprtc (also: environment SRS_NO_JIT, for deployments without the hiprtc library)
     MSM_COMPACT,        // 0 full key (16 windows) | 1 compact key: 8 windows + the curve endomorphism (half the key's HBM, no 20-bit table) | 2 compact key that may also hold a 7-window 20-bit table (msm_wide's rule; 15 windows per base); read when a key is created
     PG_COMPAT_TREE,     // 1: the reference's leaf rows (reference_compat) through the hoisted leaf passes and the weighted trees instead of the closed-form sums
+    PG_JIT_FORCE,       // 1 (developer): the run-time compiled ProtoGalaxy leaf kernels also for a gate set that has ahead-of-time ones (the bit-for-bit comparison and the timing A/B of the two)
+    PG_JIT_WAVES,       // 0 auto | 1, 2 (developer): the waves per SIMD the run-time compiled ProtoGalaxy leaf kernels are bounded for (__launch_bounds__(128, n)); read when the unit is compiled
     N_TUNABLES
 };
 

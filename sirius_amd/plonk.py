@@ -93,6 +93,26 @@ class PlonkStructure:
         dp = dev_copy.data_ptr() if _is_torch(dev_copy) else dev_copy.ctypes.data
         L.check(L.lib().srs_structure_upload_shard_halo(self._h, a.ctypes.data, dp, a.shape[0], int(bool(reference_compat)), _stream()))
 
+    def kernel_kind(self, which):
+        """Which kernels the structure's row programs run on (srs_structure_kernel_kind): which = 0 cross terms, 1 gates (deciders),
+        2 ProtoGalaxy leaves -> 0 interpreter, 1 ahead of time, 2 compiled at run time."""
+        kind = L.lib().srs_structure_kernel_kind(self._h, which)
+        assert kind >= 0, "bad argument"
+        return kind
+
+    def prepare_pg_leaves(self):
+        """Compile the ProtoGalaxy leaf kernels of this gate set now (srs_structure_prepare_pg_leaves) instead of inside the first
+        call with reference_compat=False; call it right after creation when the intended leaf rows will be used.  -> hiprtc's seconds
+        (0.0 when the structure already had compiled or ahead-of-time kernels).  SiriusAmdError rc 10 when the structure is excluded
+        (the message says why), rc 4 with the compiler log when the compile failed: the interpreter stays, results are the same."""
+        secs = C.c_double()
+        log = C.create_string_buffer(1 << 16)
+        rc = L.lib().srs_structure_prepare_pg_leaves(self._h, C.byref(secs), log, len(log))
+        if rc == L.ERR_INVALID and log.value:
+            raise L.SiriusAmdError(rc, (L.lib().srs_last_error() or b"").decode(errors="replace") + "\n" + log.value.decode(errors="replace")[-4000:])
+        L.check(rc)
+        return secs.value
+
     def close(self):
         if getattr(self, "_h", None):
             L.lib().srs_structure_free(self._h)
