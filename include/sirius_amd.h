@@ -71,9 +71,10 @@ const char *srs_version(void);
  * (or moves the size threshold between them); none changes a result.  Tests use them to run a large-input path on an input the CPU
  * oracle can check; a deployer may set "msm_wide" = 0 to save 13/16 of a large key's HBM (also: environment SRS_MSM_WIDE=0), or
  * "msm_compact" = 1 before creating a key to halve its 16-bit-window table (8 windows + the curve endomorphism, srs_ck_is_compact), or
- * "msm_compact" = 2 for such a key that may also hold a 20-bit table of 7 windows (by the rule of "msm_wide": 15 windows per base in all).
+ * "msm_compact" = 2 for such a key that may also hold a 20-bit table of 7 windows (by the rule of "msm_wide": 15 windows per base in all), or
+ * "msm_plain" = 1 for a key that is its bases alone (no window table: 1/16 of the HBM, no set-up, more work per MSM; srs_ck_is_plain).
  * Names (srs_tuning_name(i), i = 0, 1, ... until NULL): msm_sort, msm_l0, msm_wide, msm_wide_min, msm_slots, msm_slot_log,
- * msm_expect_ovf, msm_quad_max, commit_chunks, pg_f_eval, pg_g_fft, jit_always, no_jit, msm_compact, pg_compat_tree, pg_jit_force, pg_jit_waves.  Process-wide; set before the calls they
+ * msm_expect_ovf, msm_quad_max, commit_chunks, pg_f_eval, pg_g_fft, jit_always, no_jit, msm_compact, pg_compat_tree, pg_jit_force, pg_jit_waves, msm_plain.  Process-wide; set before the calls they
  * affect (a value is read when a call starts).  rc SRS_ERR_INVALID for an unknown name.  No reference counterpart. */
 int srs_tuning_set(const char *name, int64_t value);
 int srs_tuning_get(const char *name, int64_t *value);        /* *value = INT64_MIN while unset */
@@ -193,7 +194,7 @@ int srs_ck_msm_stats(const srs_ck *ck, uint64_t *out4);
 /* 1 when the key also holds the second table of the 20-bit pipeline, 13 windows -- 7 on a compact key created under "msm_compact" = 2
  * -- (keys of >= 2^23 bases: + 81 % key memory; whole
  * device-resident MSMs of >= 2^23 scalars use it), 0 when it does not -- by size, by SRS_MSM_WIDE=0, or because the device could not hold
- * it (the key then works on the 16-bit windows alone).  Multi-device keys: 1 when every shard holds it. */
+ * it (the key then works on the 16-bit windows alone).  Multi-device keys: 1 when every shard holds it.  Always 0 on a plain key. */
 int srs_ck_has_wide_table(const srs_ck *ck);
 /* Compact keys (tunable "msm_compact" = 1 when the key is created, by any creation entry; default 0).  bn256 G1 and grumpkin have the
  * endomorphism phi(x, y) = (beta x, y) = [lambda](x, y): a scalar splits as k = k1 + lambda k2 with |k1|, |k2| < 2^127, so the upper
@@ -205,10 +206,19 @@ int srs_ck_has_wide_table(const srs_ck *ck);
  * of the split scalar is below 2^126, so that table has 7 windows, not 13: such a key holds 8 + 7 = 15 windows per base
  * (srs_ck_table_bytes = len * 64 * 15, srs_ck_is_compact = srs_ck_has_wide_table = 1), and whole device-resident MSMs of >= 2^23
  * scalars take 14 digits of 20 bits per scalar instead of 16 of 16 bits.  "msm_compact" = 1 never builds it.
- * srs_ck_is_compact: 1 / 0.  srs_ck_table_bytes: bytes of window tables (16-bit and 20-bit) this rank holds -- all shards of a
- * multi-device key.  No reference counterpart. */
+ * srs_ck_is_compact: 1 / 0 (0 on a plain key).  srs_ck_table_bytes: bytes of window tables (16-bit and 20-bit) this rank holds -- all
+ * shards of a multi-device key; on a plain key the bases themselves, len * 64.  No reference counterpart. */
 int srs_ck_is_compact(const srs_ck *ck);
 size_t srs_ck_table_bytes(const srs_ck *ck);
+/* Plain keys (tunable "msm_plain" = 1 when the key is created, by any creation entry; default 0): the key is the reference's Vec<C>, its
+ * bases and nothing else -- 64 bytes per base, no window expansion at creation.  Every MSM over it, of any size, recodes the scalars into
+ * 16 signed 16-bit digits, groups them by window, accumulates the 16 windows' buckets from the bases and weights window w by 2^(16 w)
+ * with 240 doublings at its end: the same additions per scalar as a full key, plus 16 bucket reductions per MSM, so small MSMs are
+ * slower (README).  Same entries, same results bit for bit; a streamed commit runs every chunk as a whole MSM.
+ * Refused with SRS_ERR_INVALID (srs_last_error names the tunables): "msm_plain" = 1 together with "msm_compact" != 0, and a plain key
+ * spread over ranks or devices (world > 1; srs_ck_create_multi / srs_ck_setup_synthetic_multi over more than one device).
+ * srs_ck_is_plain: 1 / 0.  No reference counterpart. */
+int srs_ck_is_plain(const srs_ck *ck);
 /* Host-only diagnostics of the split (no device needed, no reference counterpart).  srs_glv_constants: lambda (scalar field) and
  * beta (base field) of `curve` as canonical integers, 4 x u64 little-endian.  srs_glv_decompose: k (repr as elsewhere) ->
  * |k1|, |k2| (canonical integers) and their signs (1 = negative), by the very body the digit kernel runs:

@@ -133,9 +133,14 @@ class CommitmentKey:
         msm_compact=2: such a key may also hold the 7-window wide table, see has_wide_table)."""
         return bool(L.lib().srs_ck_is_compact(self._h))
 
+    def is_plain(self):
+        """True when the key is its bases alone (created under tuning msm_plain=1): no window table, every MSM weights its 16 windows
+        by doublings (srs_ck_is_plain)."""
+        return bool(L.lib().srs_ck_is_plain(self._h))
+
     def table_bytes(self):
         """Bytes of window tables this key holds on its device(s) (srs_ck_table_bytes): 64 per base and window -- 16 (+ 13 wide) windows on a
-        full key, 8 (+ 7 wide under msm_compact=2) on a compact one."""
+        full key, 8 (+ 7 wide under msm_compact=2) on a compact one, 1 (the bases) on a plain one."""
         return int(L.lib().srs_ck_table_bytes(self._h))
 
     @classmethod

@@ -516,6 +516,20 @@ void free_shards(srs_ck *ck) {
     ck->shards.clear();
 }
 
+// Plain keys (tuning msm_plain = 1, msm.h) are single-rank, single-device keys, and plain or compact, not both: every creation entry asks
+// here before it allocates anything.  -> SRS_OK, or SRS_ERR_INVALID with the reason set
+static int check_key_form(uint32_t world, const char *entry) {
+    if (tuning::get_or(tuning::MSM_PLAIN, 0) != 1) return SRS_OK;
+    const int64_t compact = tuning::get_or(tuning::MSM_COMPACT, 0);
+    if (compact != 0)
+        return fail(SRS_ERR_INVALID, std::string(entry) + ": msm_plain = 1 and msm_compact = " + std::to_string(compact) +
+                                         " are both set: a key is plain (the bases alone) or compact (8 windows), choose one");
+    if (world > 1)
+        return fail(SRS_ERR_INVALID, std::string(entry) + ": msm_plain = 1: a plain key cannot be spread over " + std::to_string(world) +
+                                         " ranks or devices (create it with world = 1 on one device, or unset msm_plain)");
+    return SRS_OK;
+}
+
 // builds the shards of a multi-device key: `fill(shard)` must leave table[0 .. key.len) (window 0) on the shard's device
 template <class Fill>
 int create_multi(int curve, size_t len, int n_devices, Fill fill, srs_ck **out) {
@@ -523,6 +537,7 @@ int create_multi(int curve, size_t len, int n_devices, Fill fill, srs_ck **out) 
     if (phys <= 0) return fail(SRS_ERR_DEVICE, "no HIP device visible: libsirius_amd has no CPU path");
     const uint32_t world = n_devices > 0 ? (uint32_t)n_devices : (uint32_t)phys;
     if (world > 64) return fail(SRS_ERR_INVALID, "srs_ck_create_multi: more than 64 shards");
+    if (int rc = check_key_form(world, "srs_ck_create_multi")) return rc;
     const int home = home_device();
     srs_ck *ck = new srs_ck();
     ck->key.curve = curve;
@@ -728,7 +743,9 @@ int srs_ck_create_sharded(int curve, const srs_affine *bases, size_t len, int sp
     if (!valid_curve(curve) || !out || (!bases && len) || world == 0 || rank >= world)
         return fail(SRS_ERR_INVALID, "srs_ck_create: bad argument");
     if (len > ((size_t)1 << 27)) return fail(SRS_ERR_INVALID, "srs_ck_create: key longer than 2^27 bases");
-    int rc = ensure_device();
+    int rc = check_key_form(world, "srs_ck_create");
+    if (rc) return rc;
+    rc = ensure_device();
     if (rc) return rc;
     return guarded([&]() -> int {
         srs_ck *ck = new srs_ck();
@@ -760,7 +777,9 @@ int srs_ck_create_sharded(int curve, const srs_affine *bases, size_t len, int sp
 int srs_ck_setup_synthetic(int curve, size_t len, uint64_t seed, uint32_t rank, uint32_t world, srs_ck **out) {
     if (!valid_curve(curve) || !out || world == 0 || rank >= world) return fail(SRS_ERR_INVALID, "srs_ck_setup_synthetic: bad argument");
     if (len > ((size_t)1 << 27)) return fail(SRS_ERR_INVALID, "srs_ck_setup_synthetic: key longer than 2^27 bases");
-    int rc = ensure_device();
+    int rc = check_key_form(world, "srs_ck_setup_synthetic");
+    if (rc) return rc;
+    rc = ensure_device();
     if (rc) return rc;
     return guarded([&]() -> int {
         srs_ck *ck = new srs_ck();
@@ -825,7 +844,9 @@ int srs_ck_load_file(int curve, const char *path, size_t k, uint32_t rank, uint3
     if (k > 27) return fail(SRS_ERR_INVALID, "srs_ck_load_file: key longer than 2^27 bases");      // srs_ck_create's limit, before any allocation
     const size_t len = (size_t)1 << k;
     std::vector<srs_affine> host;
-    int rc = guarded([&]() -> int {
+    int rc = check_key_form(world, "srs_ck_load_file");            // before the file is read
+    if (rc) return rc;
+    rc = guarded([&]() -> int {
         host.resize(len);
         FILE *f = std::fopen(path, "rb");
         if (!f) return fail(SRS_ERR_IO, std::string("srs_ck_load_file: cannot open ") + path);
@@ -948,6 +969,14 @@ int srs_ck_is_compact(const srs_ck *ck) {
         if (!k.compact) compact = 0;
     });
     return compact;
+}
+int srs_ck_is_plain(const srs_ck *ck) {
+    if (!ck) return 0;
+    int plain = 1;                           // a plain key is one key on one device; an empty one is plain too (its form is decided)
+    for_each_key(ck, [&](const msm::Key &k, const CkShard *) {
+        if (!k.plain) plain = 0;
+    });
+    return plain;
 }
 size_t srs_ck_table_bytes(const srs_ck *ck) {
     if (!ck) return 0;
@@ -1152,8 +1181,9 @@ int commit_streamed_core(StreamRes ck_, const std::vector<Seg> &segs, size_t n, 
     SRS_HIP_CHECK(hipEventRecord(ck->events[chunks], st));
     SRS_HIP_CHECK(hipStreamWaitEvent(ck->copy_stream, ck->events[chunks], 0));
     std::vector<bool> launched(sets, false);
-    // every chunk on the 16-bit windows: the chunks fold their buckets into one running set and only the last one is reduced
-    bool fold = sets > 1;
+    // every chunk on the 16-bit windows: the chunks fold their buckets into one running set and only the last one is reduced.  A plain key has
+    // no running buckets (msm.h): every chunk is a whole MSM over its base range, still behind its own upload, and the results are added below
+    bool fold = sets > 1 && !ck->key.plain;
     for (size_t j = 0; j < chunks; ++j) fold = fold && sp.count(cut[j], cut[j + 1]) > 0;
     for (size_t t = 0; t < tails; ++t) fold = fold && tail->cut[t + 1] > tail->cut[t];
     auto fold_of = [&](size_t j) { return !fold ? msm::FOLD_NONE : (j == 0 ? msm::FOLD_FIRST : (j + 1 == sets ? msm::FOLD_LAST : msm::FOLD_MIDDLE)); };

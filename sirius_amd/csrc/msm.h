@@ -72,6 +72,10 @@ inline bool expect_ovf_initial() { return tuning::get_or(tuning::MSM_EXPECT_OVF,
 // Created under msm_compact = 2 the key may also carry a wide table (wants_wide_table, as for full keys) -- of NWIN_WC = 7 windows, not 13:
 // the wide flow then takes 7 signed 20-bit digits of |k1| and 7 of |k2| (rows 7..13 flagged PAY_ENDO), 8 + 7 = 15 windows per base in all.
 // msm_compact = 1 never has one.
+// A PLAIN key (tuning msm_plain = 1 at creation) holds window 0 alone: table[i] = P_i, 64 bytes per base.  An MSM over it groups its
+// signed 16-bit digits by WINDOW (the plain flow, msm.hip), runs the 16 windows as 16 linked bucket sets that all gather from that one
+// window, and finish() weights window w by 2^(16 w) with a Horner chain of doublings.  No table_w, no slot mode, no fold, no hot-bucket
+// prediction; single-rank keys only (capi.hip refuses the rest).
 struct Key {
     int curve = 0;            // 0 bn256 G1, 1 grumpkin
     size_t len = 0;           // number of bases held by THIS rank
@@ -79,7 +83,8 @@ struct Key {
     uint32_t rank = 0, world = 1;
     bool compact = false;     // 8-window table + endomorphism (choose_windows, before the table is allocated)
     bool compact_wide = false;   // a compact key that may carry the 7-window wide table (msm_compact = 2; choose_windows)
-    bool compact_scalars = false;   // world > 1: the scalar vectors handed to run() hold ONLY this rank's stripes, gathered (multi-device keys)
+    bool plain = false;       // window 0 alone (msm_plain = 1; choose_windows)
+    bool compact_scalars = false;  // world > 1: the scalar vectors handed to run() hold ONLY this rank's stripes, gathered (multi-device keys)
     affine_t *table = nullptr;
     affine_t *table_w = nullptr;   // T_w[w][i] = 2^(20 w) P_i, w < NWIN_W -- w < NWIN_WC on a compact key (keys of >= 2^WIDE_MIN_KEY_LOG bases; owned by the key: release())
     uint64_t stat_slot_sets = 0, stat_hot_sets = 0, stat_redo = 0, stat_other_sets = 0;   // srs_ck_msm_stats
@@ -90,8 +95,9 @@ struct Key {
     Arena arena;              // per-key scratch (grow-only)
     void *h_result = nullptr; // page-locked landing buffer of the 3 partial sums per MSM (direct copy, no staging hop)
     // what enqueue() left in a landing slot: the wide pipeline produced it (finish() combines 4 partial sums instead of 3); the set ran
-    // in slot mode, with its overflow kernels launched, and had this many MSMs (overflow_missed(), note_commit())
-    struct Landing { bool wide = false, slot_mode = false, ovf_on = false; uint32_t batch = 0; } landing[LANDING_SLOTS];
+    // in slot mode, with its overflow kernels launched, and had this many MSMs (overflow_missed(), note_commit()); the plain flow produced
+    // it (3 sums per WINDOW of every MSM, finish() weights the windows) for the MSMs of the mask -- the others were empty
+    struct Landing { bool wide = false, slot_mode = false, ovf_on = false; uint32_t batch = 0; bool plain = false; uint32_t plain_ran = 0; } landing[LANDING_SLOTS];
     xyzz_t *fold_buckets = nullptr;   // running bucket sums of a chunked commit (enqueue(.., fold)) outside slot mode
     // slot mode (see SLOT_LOG), grow-only
     xyzz_t *slots = nullptr;          // [batch][NBUCKET][S] persistent partial sums of the running commit
@@ -105,10 +111,11 @@ struct Key {
     uint32_t cold_streak = 0;         // commits in a row without hot buckets while they were expected
 };
 
-// decides the key's form from tuning msm_compact (read HERE, once per key) and returns the windows `table` must hold: every creation
-// entry allocates len * choose_windows(key) entries, fills window 0 and calls build_table
+// decides the key's form from tuning msm_compact and msm_plain (read HERE, once per key; both set: refused) and returns the windows `table`
+// must hold -- 1 for a plain key: every creation entry allocates len * choose_windows(key) entries, fills window 0 and calls build_table
 int choose_windows(Key &k);
-// fills table[len .. windows * len) from table[0 .. len); full keys and msm_compact = 2 keys that want it (wants_wide_table) also get table_w
+// fills table[len .. windows * len) from table[0 .. len); full keys and msm_compact = 2 keys that want it (wants_wide_table) also get table_w.
+// A plain key only has window 0 converted to the table's coordinate form.
 void build_table(Key &k, hipStream_t stream);
 // bytes of window tables the key holds (table and table_w)
 size_t table_bytes(const Key &k);
@@ -139,7 +146,8 @@ void run(Key &k, const fe_t *const *scalars_dev, const uint32_t *n_host, uint32_
 // `fold`: the sets of a chunked commit share ONE bucket set (the buckets are the digit values, whatever the base offset), and the
 // bucket reduction is linear: a set with FOLD_FIRST / FOLD_MIDDLE only adds its bucket sums into the key's running buckets (no
 // reduction, no result), the FOLD_LAST set adds its own and reduces the total -- one k_rowcol + k_reduce_final + host finish per commit
-// instead of one per chunk.  batch == 1, 16-bit-window sets only (a chunked commit never takes the wide windows).
+// instead of one per chunk.  batch == 1, 16-bit-window sets only (a chunked commit never takes the wide windows).  A plain key has no
+// running buckets: its callers pass FOLD_NONE for every chunk and add the chunks' results.
 enum Fold { FOLD_NONE = 0, FOLD_FIRST = 1, FOLD_MIDDLE = 2, FOLD_LAST = 3 };
 bool enqueue(Key &k, const fe_t *const *scalars_dev, const uint32_t *n_host, const uint32_t *base_host, uint32_t batch, int is_mont,
              hipStream_t stream, uint32_t slot, Fold fold = FOLD_NONE);

@@ -644,6 +644,32 @@ __device__ __forceinline__ void wide_codes(const WideDesc &wd, uint32_t i, uint3
     }
 }
 
+// plain keys: the NWIN signed 16-bit digits of k_digits, in the 32-bit code format above -- code[w] is the entry of WINDOW w, its bucket the
+// low 15 bits.  v = 2^16 (0xFFFF + carry) leaves magnitude 0, a zero digit that carries; the top window never carries out (scalars < 2^254).
+template <class C>
+__device__ __forceinline__ void plain_codes(const WideDesc &wd, uint32_t i, uint32_t (&code)[NWIN]) {
+    using S = typename C::S;
+    if (i >= wd.n) {
+#pragma unroll
+        for (int w = 0; w < NWIN; ++w) code[w] = 0xFFFFFFFFu;
+        return;
+    }
+    fe_t s = wd.ptr[Stripes{wd.rank, wd.world}.global_index((size_t)i)];
+    if (wd.is_mont) s = S::from_mont(s);
+    uint32_t carry = 0;
+#pragma unroll
+    for (int w = 0; w < NWIN; ++w) {
+        const uint32_t v = ((s.v[w >> 1] >> ((w & 1) * 16)) & 0xFFFFu) + carry;
+        if (v > 0x8000u) {
+            code[w] = ((0x10000u - v) - 1u) | 0x80000000u;    // negative digit, magnitude 1..0x7FFF (v = 2^16: 0xFFFFFFFF, the zero digit)
+            carry = 1;
+        } else {
+            code[w] = v ? (v - 1u) : 0xFFFFFFFFu;             // positive digit 1..0x8000, or zero
+            carry = 0;
+        }
+    }
+}
+
 // atomicAdd(ctr, 1) for the lanes with `on` set when they all name the SAME LDS counter: one atomic per wavefront (the leader reserves
 // the wavefront's slots, a lane's slot follows from the lanes below it) instead of up to 64 serialised ones.  Wave-uniform control flow
 // only.  Returns the lane's slot (meaningless where !on).  For the hot top windows of a compact key's wide flow (msm.h NWIN_WC).
@@ -667,11 +693,15 @@ __device__ __forceinline__ uint32_t wave_take(uint32_t *ctr, bool on) {
 //                  (key = low 15 bits of the bucket, payload = table index | sign << 31)
 // COMPACT (a compact key with the 7-window table, msm.h): 14 digit rows, row w gathers window w % 7 and rows 7..13 carry PAY_ENDO -- the
 // staging is sized from the digit count (512 x 14 entries, 43 KB).  Instantiations of their own: what full keys launch is compiled as before.
-template <class C, bool GROUP, bool COMPACT>
+// PLAIN (a plain key, msm.h): the 16 signed 16-bit digits of plain_codes, and the segment of an entry is its WINDOW -- the same for every
+// lane, so each counter is taken once per wavefront (wave_take); every entry gathers window 0, payload = base index | sign << 31
+// (512 x 16 entries, 48 KB of staging).
+template <class C, bool GROUP, bool COMPACT, bool PLAIN = false>
 __global__ void SRS_KERNEL_BOUNDS(WIDE_THREADS, 1)
     k_seg_pass(WideDesc wd, uint32_t *__restrict__ tile_cnt, uint32_t T, uint32_t *__restrict__ seg_total,
                uint16_t *__restrict__ gkey, uint32_t *__restrict__ gpay, uint32_t table_stride) {
-    constexpr int ND = wide_digits(COMPACT);
+    static_assert(!(PLAIN && COMPACT) && NWIN == (int)NSEG_W, "a plain key's windows are the segments");
+    constexpr int ND = PLAIN ? NWIN : wide_digits(COMPACT);
     constexpr uint32_t NW = WIDE_THREADS / 64, STAGE = GROUP ? WIDE_TILE * ND : 1;
     __shared__ uint32_t wc[NW][NSEG_W];          // counts, then (GROUP) the next free staging slot of (wavefront, segment)
     __shared__ uint32_t ss[NSEG_W + 1], goff[NSEG_W];
@@ -681,13 +711,20 @@ __global__ void SRS_KERNEL_BOUNDS(WIDE_THREADS, 1)
     if (threadIdx.x < NW * NSEG_W) (&wc[0][0])[threadIdx.x] = 0;
     uint32_t code[WIDE_PER][ND];
 #pragma unroll
-    for (uint32_t k = 0; k < WIDE_PER; ++k) wide_codes<C, COMPACT>(wd, tile * WIDE_TILE + k * WIDE_THREADS + threadIdx.x, code[k]);
+    for (uint32_t k = 0; k < WIDE_PER; ++k) {
+        const uint32_t i = tile * WIDE_TILE + k * WIDE_THREADS + threadIdx.x;
+        if constexpr (PLAIN) plain_codes<C>(wd, i, code[k]); else wide_codes<C, COMPACT>(wd, i, code[k]);
+    }
     __syncthreads();
 #pragma unroll
     for (uint32_t k = 0; k < WIDE_PER; ++k) {
 #pragma unroll
         for (int w = 0; w < ND; ++w) {
             const uint32_t c = code[k][w];
+            if (PLAIN) {                                      // segment = window: one counter for the whole wavefront
+                wave_take(&wc[wave][w], c != 0xFFFFFFFFu);
+                continue;
+            }
             if (COMPACT && (w + 1) % NWIN_WC == 0) {          // a half's top digit is <= 2^6: always segment 0, from every lane
                 wave_take(&wc[wave][0], c != 0xFFFFFFFFu);
                 continue;
@@ -736,12 +773,13 @@ __global__ void SRS_KERNEL_BOUNDS(WIDE_THREADS, 1)
 #pragma unroll
         for (int w = 0; w < ND; ++w) {
             const uint32_t c = code[k][w];
-            const bool top = COMPACT && (w + 1) % NWIN_WC == 0;
-            const uint32_t pos_top = top ? wave_take(&wc[wave][0], c != 0xFFFFFFFFu) : 0u;
+            const bool top = PLAIN || (COMPACT && (w + 1) % NWIN_WC == 0);
+            const uint32_t pos_top = top ? wave_take(&wc[wave][PLAIN ? w : 0], c != 0xFFFFFFFFu) : 0u;
             if (c != 0xFFFFFFFFu) {
                 const uint32_t pos = top ? pos_top : atomicAdd(&wc[wave][(c >> 15) & (NSEG_W - 1)], 1u);
                 skey[pos] = (uint16_t)(c & 0x7FFFu);
-                const uint32_t row = COMPACT ? ((uint32_t)w % NWIN_WC * table_stride + wd.base) | (w >= NWIN_WC ? PAY_ENDO : 0u)
+                const uint32_t row = PLAIN ? wd.base
+                                   : COMPACT ? ((uint32_t)w % NWIN_WC * table_stride + wd.base) | (w >= NWIN_WC ? PAY_ENDO : 0u)
                                              : (uint32_t)w * table_stride + wd.base;
                 spay[pos] = (row + i) | (c & 0x80000000u);
             }
@@ -1854,6 +1892,11 @@ static void build_table_t(Key &k, hipStream_t stream) {
         k.table_w = nullptr;
     }
     if (n == 0) return;
+    if (k.plain) {                           // the bases alone: no further window, no second table, only the table's coordinate form
+        SRS_LAUNCH((k_table_form<C>), (ceil_div(n, 256)), (256), 0, stream, k.table, (size_t)n);
+        SRS_HIP_CHECK(hipStreamSynchronize(stream));
+        return;
+    }
     xyzz_t *tmp = nullptr;
     SRS_HIP_CHECK(hipMalloc((void **)&tmp, (size_t)n * sizeof(xyzz_t)));
     // the second table is an optimisation (+81 % key memory): a device that cannot hold it keeps the 16-bit windows for everything
@@ -1921,6 +1964,16 @@ void build_table(Key &k, hipStream_t stream) {
 
 int choose_windows(Key &k) {
     const int64_t mode = tuning::get_or(tuning::MSM_COMPACT, 0);
+    k.plain = tuning::get_or(tuning::MSM_PLAIN, 0) == 1;
+    if (k.plain && mode != 0) {
+        set_error("msm_plain = 1 and msm_compact = " + std::to_string(mode) + " are both set: a key is plain (the bases alone) or compact (8 windows), choose one");
+        throw DeviceError{4};      // SRS_ERR_INVALID
+    }
+    if (k.plain && k.world > 1) {
+        set_error("plain key (msm_plain = 1): a key spread over " + std::to_string(k.world) + " ranks or devices is not supported");
+        throw DeviceError{4};
+    }
+    if (k.plain) return 1;
     k.compact = mode == 1 || mode == 2;
     k.compact_wide = mode == 2;              // may carry the 7-window wide table (build_table: wants_wide_table)
     // the largest index, NWIN_COMPACT * len - 1, must lie below the endomorphism flag of an entry (the wide table's NWIN_WC * len - 1 is
@@ -1935,6 +1988,7 @@ int choose_windows(Key &k) {
 }
 size_t table_bytes(const Key &k) {
     if (!k.table) return 0;
+    if (k.plain) return k.len * sizeof(affine_t);
     return k.len * sizeof(affine_t) * ((k.compact ? NWIN_COMPACT : NWIN) + (k.table_w ? (k.compact ? NWIN_WC : NWIN_W) : 0));
 }
 
@@ -2260,10 +2314,12 @@ static void reduce_buckets(const Parts &p, uint32_t nmsm, const xyzz_t *from, in
     SRS_LAUNCH((k_reduce_final<C>), (sums, nmsm), (RED_THREADS), 0, stream, (const xyzz_t *)rc, d_sums);
 }
 
-// a set's `n` partial sums into landing slot `slot` (page-locked host memory), in stream order
-static void land(Key &k, const xyzz_t *d_out, size_t n, uint32_t slot, hipStream_t stream) {
-    if (!k.h_result) SRS_HIP_CHECK(hipHostMalloc(&k.h_result, 3 * (size_t)BATCH_ARGS * LANDING_SLOTS * sizeof(xyzz_t)));
-    xyzz_t *dst = static_cast<xyzz_t *>(k.h_result) + 3 * (size_t)BATCH_ARGS * slot;
+// points of one landing slot: 3 partial sums per MSM -- per WINDOW of every MSM on a plain key
+static size_t landing_pts(const Key &k) { return 3 * (size_t)BATCH_ARGS * (k.plain ? NWIN : 1); }
+// a set's `n` partial sums into landing slot `slot` (page-locked host memory) from its point `at` on, in stream order
+static void land(Key &k, const xyzz_t *d_out, size_t n, uint32_t slot, hipStream_t stream, size_t at = 0) {
+    if (!k.h_result) SRS_HIP_CHECK(hipHostMalloc(&k.h_result, landing_pts(k) * LANDING_SLOTS * sizeof(xyzz_t)));
+    xyzz_t *dst = static_cast<xyzz_t *>(k.h_result) + landing_pts(k) * slot + at;
     SRS_HIP_CHECK(hipMemcpyAsync(dst, d_out, n * sizeof(xyzz_t), hipMemcpyDeviceToHost, stream));
 }
 
@@ -2440,41 +2496,34 @@ static bool use_wide(const Key &k, uint32_t n_max, uint32_t batch) {
     return k.table_w != nullptr && batch == 1 && n_max >= (1u << min_log);
 }
 
+// The flow of the 16 segments, shared by the wide windows and by plain keys: segment counts -> offsets -> grouping (the two passes of
+// `seg_count` / `seg_group` over the scalars), the counting sort inside the segments, level 0 over `table`, the levels and the bucket
+// reduction of the 16 segments as ONE linked batch -> `sums` partial sums per segment in b.d_seg.
 template <class C>
-static bool enqueue_wide_t(Key &k, const fe_t *scalars_dev, uint32_t n, uint32_t base, int is_mont, hipStream_t stream, uint32_t slot) {
-    const WideShape w = wide_shape(n, wide_digits(k.compact));
-    // a compact key differs in the two segment passes (split digits, 14 rows, flagged payloads), in the hot sub-segment of k_group_g and in level 0
-    const auto seg_count = k.compact ? &k_seg_pass<C, false, true> : &k_seg_pass<C, false, false>;
-    const auto seg_group = k.compact ? &k_seg_pass<C, true, true> : &k_seg_pass<C, true, false>;
-    const auto group_g = k.compact ? &k_group_g<true> : &k_group_g<false>;
-    const auto accum0 = k.compact ? &k_accum0c<C> : &k_accum0<C>;
-    const WideBufs b = carve(k.arena, [&](auto &A) { return wide_layout(A, w); });
+struct SegKernels {
+    decltype(&k_seg_pass<C, false, false>) seg_count, seg_group;
+    decltype(&k_group_g<false>) group_g;
+    decltype(&k_accum0<C>) accum0;
+};
+template <class C>
+static void segment_flow(const WideShape &w, const WideBufs &b, const WideDesc &wd, uint32_t table_stride, const SegKernels<C> &kn,
+                         const affine_t *table, uint32_t sums, hipStream_t stream) {
     uint32_t *seg_total = b.seg3, *seg_off = b.seg3 + (NSEG_W + 2), *tile_base = b.seg3 + 2 * (NSEG_W + 2), *tile_base2 = b.seg3 + 3 * (NSEG_W + 2);
-
-    WideDesc wd;
-    wd.ptr = scalars_dev;
-    wd.n = n;
-    wd.base = base;
-    wd.rank = k.compact_scalars ? 0u : k.rank;
-    wd.world = k.compact_scalars ? 1u : k.world;
-    wd.is_mont = is_mont;
-    const uint32_t table_stride = (uint32_t)k.len;
-
     // sort: segment counts -> offsets -> grouping (MSD pass), then the counting sort inside the segments
     SRS_HIP_CHECK(hipMemsetAsync(seg_total, 0, (NSEG_W + 1) * sizeof(uint32_t), stream));
     SRS_HIP_CHECK(hipMemsetAsync(b.count, 0, (size_t)NSEG_W * NBUCKET * sizeof(uint32_t), stream));
-    SRS_LAUNCH(seg_count, (w.T), (WIDE_THREADS), 0, stream, wd, b.tile_cnt, w.T, seg_total, (uint16_t *)nullptr,
+    SRS_LAUNCH(kn.seg_count, (w.T), (WIDE_THREADS), 0, stream, wd, b.tile_cnt, w.T, seg_total, (uint16_t *)nullptr,
                (uint32_t *)nullptr, table_stride);
     const uint32_t small_tiles = (w.M >> 19) < 64 ? 1u : 0u, tile2_host = small_tiles ? SORT_TILE2 / 4 : SORT_TILE2;
     SRS_LAUNCH(k_seg_scan, (NSEG_W), (1024), 0, stream, b.tile_cnt, w.T, (const uint32_t *)seg_total, seg_off, tile_base, tile_base2, small_tiles);
-    SRS_LAUNCH(seg_group, (w.T), (WIDE_THREADS), 0, stream, wd, b.tile_cnt, w.T, seg_total, b.gkey, b.gpay, table_stride);
+    SRS_LAUNCH(kn.seg_group, (w.T), (WIDE_THREADS), 0, stream, wd, b.tile_cnt, w.T, seg_total, b.gkey, b.gpay, table_stride);
     SRS_LAUNCH(k_hist_g, (w.tiles_g), (SORT_THREADS), 0, stream, (const uint16_t *)b.gkey, (const uint32_t *)seg_off,
                (const uint32_t *)tile_base, b.count, b.tile_hist);
     SRS_LAUNCH(k_plan, (NSEG_W, w.levels + 1), (PLAN_THREADS), 0, stream, (const uint32_t *)b.count, b.cursor, b.plan, w.plan_stride, w.levels,
                w.l0_log, (uint32_t)ACC_L1_LOG, (const uint32_t *)seg_off);
     SRS_LAUNCH(k_scan_seg_g, (SEG, NSEG_W), (1024), 0, stream, b.tile_hist, w.tiles_g, (const uint32_t *)tile_base, (const uint32_t *)b.plan,
                w.plan_stride);
-    SRS_LAUNCH(group_g, (w.tiles_g), (SORT_THREADS), 0, stream, (const uint16_t *)b.gkey, (const uint32_t *)b.gpay, (const uint32_t *)seg_off,
+    SRS_LAUNCH(kn.group_g, (w.tiles_g), (SORT_THREADS), 0, stream, (const uint16_t *)b.gkey, (const uint32_t *)b.gpay, (const uint32_t *)seg_off,
                (const uint32_t *)tile_base, (const uint32_t *)b.tile_hist, b.gkey2, b.gpay2);
     // tiles of SORT_TILE2 entries cut per segment: at most M / SORT_TILE2 + NSEG_W of them; 8 x ceil(. / 8) workgroups (XCD mapping)
     SRS_LAUNCH(k_scatter2_g, (8 * ceil_div(ceil_div(w.M, tile2_host) + NSEG_W, 8)), (SORT_THREADS), 0, stream, (const uint16_t *)b.gkey2,
@@ -2483,16 +2532,80 @@ static bool enqueue_wide_t(Key &k, const fe_t *scalars_dev, uint32_t n, uint32_t
     // from here on the 16 segments are ONE linked batch: no strides, the link says where a segment's parts start
     const Parts p{b.plan, w.plan_stride, b.ping, 0, b.pong, 0, b.link};
     SRS_LAUNCH(k_expand, (NBUCKET / 4, NSEG_W), (256), 0, stream, p.plan, p.plan_stride, b.tb, (size_t)0, p.link, 1u);
-    SRS_LAUNCH_TIMED("msm_accum0", n, accum0, (ceil_div(w.cap0, ACC_THREADS)), (ACC_THREADS), 0, stream, (const uint32_t *)b.sorted,
-                     (size_t)0, p.plan, p.plan_stride, (const uint16_t *)b.tb, (size_t)0, (const affine_t *)k.table_w, p.ping, (size_t)0,
+    SRS_LAUNCH_TIMED("msm_accum0", wd.n, kn.accum0, (ceil_div(w.cap0, ACC_THREADS)), (ACC_THREADS), 0, stream, (const uint32_t *)b.sorted,
+                     (size_t)0, p.plan, p.plan_stride, (const uint16_t *)b.tb, (size_t)0, table, p.ping, (size_t)0,
                      1u << w.l0_log, p.link);
     accum_levels<C>(p, w, (uint64_t)NSEG_W * (NBUCKET + 1), 1, stream);
     SRS_LAUNCH((k_accum_final<C>), (NBUCKET / (FINAL_THREADS / 64), NSEG_W), (FINAL_THREADS), 0, stream, (const xyzz_t *)p.ping, p.stride0,
                (const xyzz_t *)p.pong, p.stride1, p.plan, p.plan_stride, b.buckets, p.link);
-    reduce_buckets<C>(p, NSEG_W, b.buckets, 0, b.rc, 4, b.d_seg, stream);
+    reduce_buckets<C>(p, NSEG_W, b.buckets, 0, b.rc, sums, b.d_seg, stream);
+}
+
+template <class C>
+static bool enqueue_wide_t(Key &k, const fe_t *scalars_dev, uint32_t n, uint32_t base, int is_mont, hipStream_t stream, uint32_t slot) {
+    const WideShape w = wide_shape(n, wide_digits(k.compact));
+    // a compact key differs in the two segment passes (split digits, 14 rows, flagged payloads), in the hot sub-segment of k_group_g and in level 0
+    const SegKernels<C> kn = k.compact ? SegKernels<C>{&k_seg_pass<C, false, true>, &k_seg_pass<C, true, true>, &k_group_g<true>, &k_accum0c<C>}
+                                       : SegKernels<C>{&k_seg_pass<C, false, false>, &k_seg_pass<C, true, false>, &k_group_g<false>, &k_accum0<C>};
+    const WideBufs b = carve(k.arena, [&](auto &A) { return wide_layout(A, w); });
+    const WideDesc wd{scalars_dev, n, base, k.compact_scalars ? 0u : k.rank, k.compact_scalars ? 1u : k.world, is_mont};
+    segment_flow<C>(w, b, wd, (uint32_t)k.len, kn, k.table_w, 4, stream);
     SRS_LAUNCH((k_wide_combine<C>), (1), (256), 0, stream, (const xyzz_t *)b.d_seg, b.d_out);
     land(k, b.d_out, 4, slot, stream);
     k.landing[slot].wide = true;
+    return true;
+}
+
+// ---- the plain flow: ONE MSM of any size over a plain key (window 0 alone) ------------------------------------------------------------
+// The wide flow (segment_flow) with the WINDOW as the segment: k_seg_pass<PLAIN> groups the 16 n signed 16-bit digits by window, and from
+// k_hist_g to reduce_buckets the 16 windows are the 16 linked segments -- every entry gathers from k.table, the bases.  What leaves is 3 partial sums
+// per window, landed at point 3 NWIN m of the slot; finish_t weights the windows.  MSM m of a batch is one such flow after the other on
+// the stream: they share the arena in stream order (the caller has reserved it for the largest of them).
+static WideShape plain_shape(uint32_t n) { return wide_shape(n, NWIN); }
+// what the flows of up to n_max scalars need.  The layout grows with n while the part length stays (wide_shape), but a longer part shrinks
+// ping / pong: the largest n of every shorter part length is a candidate too, so that a smaller MSM later on the stream never grows the arena
+static size_t workspace_bytes_plain(uint32_t n_max) {
+    size_t need = 0;
+    for (uint32_t n = n_max; n;) {
+        need = std::max(need, sized([&](auto &A) { return wide_layout(A, plain_shape(n)); }));
+        const uint32_t lg = l0_log_for((uint64_t)n * NWIN);
+        uint32_t lo = 1, hi = n;                               // smallest count with this part length
+        while (lo < hi) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if (l0_log_for((uint64_t)mid * NWIN) == lg) hi = mid; else lo = mid + 1;
+        }
+        n = lo - 1;
+    }
+    return need;
+}
+
+template <class C>
+static void enqueue_plain_t(Key &k, const fe_t *scalars_dev, uint32_t n, uint32_t base, int is_mont, hipStream_t stream, uint32_t slot,
+                            uint32_t m) {
+    const WideShape w = plain_shape(n);
+    const SegKernels<C> kn{&k_seg_pass<C, false, false, true>, &k_seg_pass<C, true, false, true>, &k_group_g<false>, &k_accum0<C>};
+    const WideBufs b = carve(k.arena, [&](auto &A) { return wide_layout(A, w); });
+    const WideDesc wd{scalars_dev, n, base, 0u, 1u, is_mont};            // a plain key is never sharded (choose_windows)
+    segment_flow<C>(w, b, wd, 0u, kn, k.table, 3, stream);
+    land(k, b.d_seg, 3 * (size_t)NWIN, slot, stream, 3 * (size_t)NWIN * m);
+}
+
+// a set of <= BATCH_ARGS MSMs on a plain key.  Returns false when every MSM is empty (nothing was launched).
+template <class C>
+static bool enqueue_plain_set_t(Key &k, const fe_t *const *scalars_dev, const uint32_t *n_host, const uint32_t *base_host, uint32_t batch,
+                                int is_mont, hipStream_t stream, uint32_t slot) {
+    uint32_t n_max = 0, ran = 0;
+    for (uint32_t m = 0; m < batch; ++m) n_max = std::max(n_max, n_host[m]);
+    if (n_max == 0) return false;
+    k.arena.reserve(workspace_bytes_plain(n_max));          // before the first launch: growing it between two flows would free memory in use
+    for (uint32_t m = 0; m < batch; ++m) {
+        if (n_host[m] == 0) continue;
+        enqueue_plain_t<C>(k, scalars_dev[m], n_host[m], base_host ? base_host[m] : 0u, is_mont, stream, slot, m);
+        ran |= 1u << m;
+    }
+    k.landing[slot].wide = false;
+    k.landing[slot].plain = true;
+    k.landing[slot].plain_ran = ran;
     return true;
 }
 
@@ -2503,23 +2616,36 @@ static void finish_t(Key &k, uint32_t batch, uint32_t slot, bool launched, xyzz_
         for (uint32_t m = 0; m < batch; ++m) result_host[m] = Ec<C>::identity();
         return;
     }
-    const xyzz_t *raw = static_cast<const xyzz_t *>(k.h_result) + 3 * (size_t)BATCH_ARGS * slot;
+    const xyzz_t *raw = static_cast<const xyzz_t *>(k.h_result) + landing_pts(k) * slot;
     // the device sums arrive in the R' = 2^261 form of the 29-bit multiplier: times 2^-5 (as a Montgomery product) -> ABI form
     using F = typename C::F;
     fe_t c = F::one();
     for (int d = 0; d < 5; ++d) c = F::halve(c);
-    std::vector<xyzz_t> two(3 * (size_t)batch + (k.landing[slot].wide ? 1 : 0));
+    const bool plain = k.landing[slot].plain;
+    std::vector<xyzz_t> two(plain ? 3 * (size_t)NWIN * batch : 3 * (size_t)batch + (k.landing[slot].wide ? 1 : 0));
     for (size_t i = 0; i < two.size(); ++i) {
         two[i].x = F::mul(raw[i].x, c);
         two[i].y = F::mul(raw[i].y, c);
         two[i].zz = F::mul(raw[i].zz, c);
         two[i].zzz = F::mul(raw[i].zzz, c);
     }
-    for (uint32_t m = 0; m < batch; ++m) {
-        xyzz_t a = Ec<C>::add(Ec<C>::dbl(two[3 * m]), two[3 * m + 2]);
+    const auto bucket_sum = [&](size_t at) {                    // of the 3 partial sums from `at` on
+        xyzz_t a = Ec<C>::add(Ec<C>::dbl(two[at]), two[at + 2]);
         for (uint32_t j = 1; j < RED_COLS; j <<= 1) a = Ec<C>::dbl(a);
-        result_host[m] = Ec<C>::add(a, two[3 * m + 1]);
+        return Ec<C>::add(a, two[at + 1]);
+    };
+    if (plain) {                                                // sum_w 2^(16 w) R_w as a Horner chain from the top window: 240 doublings, 15 additions
+        for (uint32_t m = 0; m < batch; ++m) {
+            xyzz_t acc = Ec<C>::identity();
+            for (int w = NWIN - 1; w >= 0 && (k.landing[slot].plain_ran >> m & 1u); --w) {
+                for (int d = 0; d < WBITS && w != NWIN - 1; ++d) acc = Ec<C>::dbl(acc);
+                acc = Ec<C>::add(acc, bucket_sum(3 * ((size_t)NWIN * m + w)));
+            }
+            result_host[m] = acc;
+        }
+        return;
     }
+    for (uint32_t m = 0; m < batch; ++m) result_host[m] = bucket_sum(3 * (size_t)m);
     if (k.landing[slot].wide) {                                 // one MSM, 4 sums: + NBUCKET * U for the segment totals
         xyzz_t u = two[3];
         for (uint32_t j = 1; j < NBUCKET; j <<= 1) u = Ec<C>::dbl(u);
@@ -2536,6 +2662,16 @@ bool enqueue(Key &k, const fe_t *const *scalars_dev, const uint32_t *n_host, con
     if (fold != FOLD_NONE && batch != 1) {
         set_error("internal: msm::enqueue fold needs one MSM per set");
         throw DeviceError{5};
+    }
+    if (k.plain) {                           // every set, whatever its size: no slot mode, no fold, no wide table
+        if (fold != FOLD_NONE) {
+            set_error("internal: msm::enqueue fold on a plain key");
+            throw DeviceError{5};
+        }
+        k.landing[slot].slot_mode = false;
+        ++k.stat_other_sets;
+        return k.curve == 0 ? enqueue_plain_set_t<Bn256>(k, scalars_dev, n_host, base_host, batch, is_mont, stream, slot)
+                            : enqueue_plain_set_t<Grumpkin>(k, scalars_dev, n_host, base_host, batch, is_mont, stream, slot);
     }
     if (batch == 1 && fold == FOLD_NONE && use_wide(k, n_host[0], 1)) {      // the sets of a chunked commit stay on the 16-bit windows
         const uint32_t base = base_host ? base_host[0] : 0;
@@ -2562,6 +2698,10 @@ void finish(Key &k, uint32_t batch, uint32_t slot, bool launched, xyzz_t *result
     if (k.curve == 0) finish_t<Bn256>(k, batch, slot, launched, result_host); else finish_t<Grumpkin>(k, batch, slot, launched, result_host);
 }
 void reserve(Key &k, uint32_t n_max, uint32_t batch) {
+    if (k.plain) {                           // the MSMs of a batch run one after the other in one arena
+        k.arena.reserve(workspace_bytes_plain(n_max));
+        return;
+    }
     size_t b = use_wide(k, n_max, batch) ? std::max(workspace_bytes_wide(n_max, wide_digits(k.compact)), workspace_bytes(n_max, batch))
                                          : workspace_bytes(n_max, batch);
     if (batch == 1) b = std::max(b, workspace_bytes_slots(n_max, batch));        // (a chunked commit's sets: slot mode)
