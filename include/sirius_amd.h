@@ -72,7 +72,8 @@ const char *srs_version(void);
  * oracle can check; a deployer may set "msm_wide" = 0 to save 13/16 of a large key's HBM (also: environment SRS_MSM_WIDE=0), or
  * "msm_compact" = 1 before creating a key to halve its 16-bit-window table (8 windows + the curve endomorphism, srs_ck_is_compact), or
  * "msm_compact" = 2 for such a key that may also hold a 20-bit table of 7 windows (by the rule of "msm_wide": 15 windows per base in all), or
- * "msm_plain" = 1 for a key that is its bases alone (no window table: 1/16 of the HBM, no set-up, more work per MSM; srs_ck_is_plain).
+ * "msm_plain" = 1 for a key that is its bases alone (no window table: 1/16 of the HBM, no set-up, more work per MSM; srs_ck_is_plain), or
+ * "msm_plain" = 2 for the same key whose MSMs take 8 windows through the endomorphism instead of 16.
  * Names (srs_tuning_name(i), i = 0, 1, ... until NULL): msm_sort, msm_l0, msm_wide, msm_wide_min, msm_slots, msm_slot_log,
  * msm_expect_ovf, msm_quad_max, commit_chunks, pg_f_eval, pg_g_fft, jit_always, no_jit, msm_compact, pg_compat_tree, pg_jit_force, pg_jit_waves, msm_plain.  Process-wide; set before the calls they
  * affect (a value is read when a call starts).  rc SRS_ERR_INVALID for an unknown name.  No reference counterpart. */
@@ -215,9 +216,13 @@ size_t srs_ck_table_bytes(const srs_ck *ck);
  * 16 signed 16-bit digits, groups them by window, accumulates the 16 windows' buckets from the bases and weights window w by 2^(16 w)
  * with 240 doublings at its end: the same additions per scalar as a full key, plus 16 bucket reductions per MSM, so small MSMs are
  * slower (README).  Same entries, same results bit for bit; a streamed commit runs every chunk as a whole MSM.
- * Refused with SRS_ERR_INVALID (srs_last_error names the tunables): "msm_plain" = 1 together with "msm_compact" != 0, and a plain key
+ * "msm_plain" = 2 is the same key in memory (64 bytes per base, no window expansion) whose MSMs split the scalar as a compact key does,
+ * k = k1 + lambda k2: 8 signed 16-bit digits of k1 and 8 of k2, digit w of either in window w, the entries of k2 gathering
+ * phi(P) = (beta x, y) from the same base for one field product.  8 bucket reductions and 112 doublings per MSM instead of 16 and 240: the
+ * smaller fixed cost per MSM, for one more product per entry of k2 (INTEGRATION.md 4c says which form to choose when).
+ * Refused with SRS_ERR_INVALID (srs_last_error names the tunables): "msm_plain" = 1 or 2 together with "msm_compact" != 0, and a plain key
  * spread over ranks or devices (world > 1; srs_ck_create_multi / srs_ck_setup_synthetic_multi over more than one device).
- * srs_ck_is_plain: 1 / 0.  No reference counterpart. */
+ * srs_ck_is_plain: the form, 1 or 2, of a plain key; 0 for every other key.  No reference counterpart. */
 int srs_ck_is_plain(const srs_ck *ck);
 /* Host-only diagnostics of the split (no device needed, no reference counterpart).  srs_glv_constants: lambda (scalar field) and
  * beta (base field) of `curve` as canonical integers, 4 x u64 little-endian.  srs_glv_decompose: k (repr as elsewhere) ->

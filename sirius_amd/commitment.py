@@ -134,9 +134,14 @@ class CommitmentKey:
         return bool(L.lib().srs_ck_is_compact(self._h))
 
     def is_plain(self):
-        """True when the key is its bases alone (created under tuning msm_plain=1): no window table, every MSM weights its 16 windows
+        """True when the key is its bases alone (created under tuning msm_plain=1 or 2): no window table, every MSM weights its windows
         by doublings (srs_ck_is_plain)."""
         return bool(L.lib().srs_ck_is_plain(self._h))
+
+    def plain_form(self):
+        """0 for a key with window tables; 1 for a plain key whose MSMs run 16 windows; 2 for one whose MSMs run 8 windows over the split
+        scalar (msm_plain=2, the endomorphism).  The value of srs_ck_is_plain."""
+        return int(L.lib().srs_ck_is_plain(self._h))
 
     def table_bytes(self):
         """Bytes of window tables this key holds on its device(s) (srs_ck_table_bytes): 64 per base and window -- 16 (+ 13 wide) windows on a

@@ -516,16 +516,18 @@ void free_shards(srs_ck *ck) {
     ck->shards.clear();
 }
 
-// Plain keys (tuning msm_plain = 1, msm.h) are single-rank, single-device keys, and plain or compact, not both: every creation entry asks
+// Plain keys (tuning msm_plain = 1 / 2, msm.h) are single-rank, single-device keys, and plain or compact, not both: every creation entry asks
 // here before it allocates anything.  -> SRS_OK, or SRS_ERR_INVALID with the reason set
 static int check_key_form(uint32_t world, const char *entry) {
-    if (tuning::get_or(tuning::MSM_PLAIN, 0) != 1) return SRS_OK;
+    const int64_t form = tuning::get_or(tuning::MSM_PLAIN, 0);
+    if (form != 1 && form != 2) return SRS_OK;
+    const std::string plain = "msm_plain = " + std::to_string(form);
     const int64_t compact = tuning::get_or(tuning::MSM_COMPACT, 0);
     if (compact != 0)
-        return fail(SRS_ERR_INVALID, std::string(entry) + ": msm_plain = 1 and msm_compact = " + std::to_string(compact) +
+        return fail(SRS_ERR_INVALID, std::string(entry) + ": " + plain + " and msm_compact = " + std::to_string(compact) +
                                          " are both set: a key is plain (the bases alone) or compact (8 windows), choose one");
     if (world > 1)
-        return fail(SRS_ERR_INVALID, std::string(entry) + ": msm_plain = 1: a plain key cannot be spread over " + std::to_string(world) +
+        return fail(SRS_ERR_INVALID, std::string(entry) + ": " + plain + ": a plain key cannot be spread over " + std::to_string(world) +
                                          " ranks or devices (create it with world = 1 on one device, or unset msm_plain)");
     return SRS_OK;
 }
@@ -972,11 +974,12 @@ int srs_ck_is_compact(const srs_ck *ck) {
 }
 int srs_ck_is_plain(const srs_ck *ck) {
     if (!ck) return 0;
-    int plain = 1;                           // a plain key is one key on one device; an empty one is plain too (its form is decided)
+    int form = -1;                           // a plain key is one key on one device; an empty one is plain too (its form is decided)
     for_each_key(ck, [&](const msm::Key &k, const CkShard *) {
-        if (!k.plain) plain = 0;
+        if (form < 0) form = k.plain_form;   // 1: sixteen windows per MSM, 2: eight, through the endomorphism
+        if (!k.plain || k.plain_form != form) form = 0;
     });
-    return plain;
+    return form < 0 ? 0 : form;
 }
 size_t srs_ck_table_bytes(const srs_ck *ck) {
     if (!ck) return 0;

@@ -76,6 +76,8 @@ inline bool expect_ovf_initial() { return tuning::get_or(tuning::MSM_EXPECT_OVF,
 // signed 16-bit digits by WINDOW (the plain flow, msm.hip), runs the 16 windows as 16 linked bucket sets that all gather from that one
 // window, and finish() weights window w by 2^(16 w) with a Horner chain of doublings.  No table_w, no slot mode, no fold, no hot-bucket
 // prediction; single-rank keys only (capi.hip refuses the rest).
+// Form 2 (msm_plain = 2) is the same key in memory; its MSMs split the scalar as a compact key does (k = k1 + lambda k2, glv.cuh) and run 8
+// windows of two entries per scalar -- those of k2 flagged PAY_ENDO, level 0 gathers phi of the base -- so 8 bucket sets and 112 doublings.
 struct Key {
     int curve = 0;            // 0 bn256 G1, 1 grumpkin
     size_t len = 0;           // number of bases held by THIS rank
@@ -83,7 +85,8 @@ struct Key {
     uint32_t rank = 0, world = 1;
     bool compact = false;     // 8-window table + endomorphism (choose_windows, before the table is allocated)
     bool compact_wide = false;   // a compact key that may carry the 7-window wide table (msm_compact = 2; choose_windows)
-    bool plain = false;       // window 0 alone (msm_plain = 1; choose_windows)
+    bool plain = false;       // window 0 alone (msm_plain = 1 / 2; choose_windows)
+    uint8_t plain_form = 0;   // 0: not plain; 1: 16 windows per MSM from the scalar's digits; 2: 8 windows from the split scalar (endomorphism)
     bool compact_scalars = false;  // world > 1: the scalar vectors handed to run() hold ONLY this rank's stripes, gathered (multi-device keys)
     affine_t *table = nullptr;
     affine_t *table_w = nullptr;   // T_w[w][i] = 2^(20 w) P_i, w < NWIN_W -- w < NWIN_WC on a compact key (keys of >= 2^WIDE_MIN_KEY_LOG bases; owned by the key: release())
@@ -96,8 +99,9 @@ struct Key {
     void *h_result = nullptr; // page-locked landing buffer of the 3 partial sums per MSM (direct copy, no staging hop)
     // what enqueue() left in a landing slot: the wide pipeline produced it (finish() combines 4 partial sums instead of 3); the set ran
     // in slot mode, with its overflow kernels launched, and had this many MSMs (overflow_missed(), note_commit()); the plain flow produced
-    // it (3 sums per WINDOW of every MSM, finish() weights the windows) for the MSMs of the mask -- the others were empty
-    struct Landing { bool wide = false, slot_mode = false, ovf_on = false; uint32_t batch = 0; bool plain = false; uint32_t plain_ran = 0; } landing[LANDING_SLOTS];
+    // it (3 sums per WINDOW of every MSM, 16 or with plain_form == 2 eight of them, finish() weights the windows) for the MSMs of the mask --
+    // the others were empty
+    struct Landing { bool wide = false, slot_mode = false, ovf_on = false; uint32_t batch = 0; bool plain = false; uint8_t plain_form = 0; uint32_t plain_ran = 0; } landing[LANDING_SLOTS];
     xyzz_t *fold_buckets = nullptr;   // running bucket sums of a chunked commit (enqueue(.., fold)) outside slot mode
     // slot mode (see SLOT_LOG), grow-only
     xyzz_t *slots = nullptr;          // [batch][NBUCKET][S] persistent partial sums of the running commit

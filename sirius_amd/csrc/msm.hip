@@ -670,6 +670,28 @@ __device__ __forceinline__ void plain_codes(const WideDesc &wd, uint32_t i, uint
     }
 }
 
+// plain keys of form 2 (msm_plain = 2): k = k1 + lambda k2 (glv.cuh), rows 0..7 the 8 signed 16-bit digits of k1, rows 8..15 those of k2,
+// in the same 32-bit code format.  Row r is an entry of WINDOW r % 8 -- phi is a homomorphism, so digit w of k2 weighs 2^(16 w) phi(P) --
+// and rows 8..15 gather phi of the base (k_seg_pass flags them PAY_ENDO).  The top window of a half never carries out: the bound
+// compact keys rely on for their 8 narrow windows (recode_half above: |k1|, |k2| < 2^126 by tools/gen_glv_consts.py, so the eighth
+// window of a half holds at most 14 bits plus the carry; the split itself is glv_decompose, glv.cuh).
+template <class C>
+__device__ __forceinline__ void plain_glv_codes(const WideDesc &wd, uint32_t i, uint32_t (&code)[NWIN]) {
+    using S = typename C::S;
+    static_assert(2 * NWIN_COMPACT == NWIN, "two halves of 8 windows fill the 16 digit rows");
+    if (i >= wd.n) {
+#pragma unroll
+        for (int w = 0; w < NWIN; ++w) code[w] = 0xFFFFFFFFu;
+        return;
+    }
+    fe_t s = wd.ptr[Stripes{wd.rank, wd.world}.global_index((size_t)i)];
+    if (wd.is_mont) s = S::from_mont(s);
+    const glv_t g = glv_decompose<C>(s);
+    const auto put = [&](int w, uint32_t mag, bool minus) { code[w] = mag ? ((mag - 1u) | (minus ? 0x80000000u : 0u)) : 0xFFFFFFFFu; };
+    recode_half<WBITS, NWIN_COMPACT>(g.k1, g.neg1, put);
+    recode_half<WBITS, NWIN_COMPACT>(g.k2, g.neg2, [&](int w, uint32_t mag, bool minus) { put(NWIN_COMPACT + w, mag, minus); });
+}
+
 // atomicAdd(ctr, 1) for the lanes with `on` set when they all name the SAME LDS counter: one atomic per wavefront (the leader reserves
 // the wavefront's slots, a lane's slot follows from the lanes below it) instead of up to 64 serialised ones.  Wave-uniform control flow
 // only.  Returns the lane's slot (meaningless where !on).  For the hot top windows of a compact key's wide flow (msm.h NWIN_WC).
@@ -696,11 +718,15 @@ __device__ __forceinline__ uint32_t wave_take(uint32_t *ctr, bool on) {
 // PLAIN (a plain key, msm.h): the 16 signed 16-bit digits of plain_codes, and the segment of an entry is its WINDOW -- the same for every
 // lane, so each counter is taken once per wavefront (wave_take); every entry gathers window 0, payload = base index | sign << 31
 // (512 x 16 entries, 48 KB of staging).
-template <class C, bool GROUP, bool COMPACT, bool PLAIN = false>
+// PLAIN with GLV (a plain key of form 2): the 16 rows of plain_glv_codes; the segment of row r is the window r % 8, still the same for every
+// lane, so a window's counter is taken twice per scalar; rows 8..15 carry PAY_ENDO (the base index stays below bit 30: keys are <= 2^27
+// bases).  Segments 8..15 stay empty.  The same staging.
+template <class C, bool GROUP, bool COMPACT, bool PLAIN = false, bool GLV = false>
 __global__ void SRS_KERNEL_BOUNDS(WIDE_THREADS, 1)
     k_seg_pass(WideDesc wd, uint32_t *__restrict__ tile_cnt, uint32_t T, uint32_t *__restrict__ seg_total,
                uint16_t *__restrict__ gkey, uint32_t *__restrict__ gpay, uint32_t table_stride) {
     static_assert(!(PLAIN && COMPACT) && NWIN == (int)NSEG_W, "a plain key's windows are the segments");
+    static_assert(PLAIN || !GLV, "GLV selects the second form of a plain key");
     constexpr int ND = PLAIN ? NWIN : wide_digits(COMPACT);
     constexpr uint32_t NW = WIDE_THREADS / 64, STAGE = GROUP ? WIDE_TILE * ND : 1;
     __shared__ uint32_t wc[NW][NSEG_W];          // counts, then (GROUP) the next free staging slot of (wavefront, segment)
@@ -713,7 +739,8 @@ __global__ void SRS_KERNEL_BOUNDS(WIDE_THREADS, 1)
 #pragma unroll
     for (uint32_t k = 0; k < WIDE_PER; ++k) {
         const uint32_t i = tile * WIDE_TILE + k * WIDE_THREADS + threadIdx.x;
-        if constexpr (PLAIN) plain_codes<C>(wd, i, code[k]); else wide_codes<C, COMPACT>(wd, i, code[k]);
+        if constexpr (PLAIN && GLV) plain_glv_codes<C>(wd, i, code[k]);
+        else if constexpr (PLAIN) plain_codes<C>(wd, i, code[k]); else wide_codes<C, COMPACT>(wd, i, code[k]);
     }
     __syncthreads();
 #pragma unroll
@@ -722,7 +749,7 @@ __global__ void SRS_KERNEL_BOUNDS(WIDE_THREADS, 1)
         for (int w = 0; w < ND; ++w) {
             const uint32_t c = code[k][w];
             if (PLAIN) {                                      // segment = window: one counter for the whole wavefront
-                wave_take(&wc[wave][w], c != 0xFFFFFFFFu);
+                wave_take(&wc[wave][GLV ? w % NWIN_COMPACT : w], c != 0xFFFFFFFFu);
                 continue;
             }
             if (COMPACT && (w + 1) % NWIN_WC == 0) {          // a half's top digit is <= 2^6: always segment 0, from every lane
@@ -774,11 +801,11 @@ __global__ void SRS_KERNEL_BOUNDS(WIDE_THREADS, 1)
         for (int w = 0; w < ND; ++w) {
             const uint32_t c = code[k][w];
             const bool top = PLAIN || (COMPACT && (w + 1) % NWIN_WC == 0);
-            const uint32_t pos_top = top ? wave_take(&wc[wave][PLAIN ? w : 0], c != 0xFFFFFFFFu) : 0u;
+            const uint32_t pos_top = top ? wave_take(&wc[wave][PLAIN ? (GLV ? w % NWIN_COMPACT : w) : 0], c != 0xFFFFFFFFu) : 0u;
             if (c != 0xFFFFFFFFu) {
                 const uint32_t pos = top ? pos_top : atomicAdd(&wc[wave][(c >> 15) & (NSEG_W - 1)], 1u);
                 skey[pos] = (uint16_t)(c & 0x7FFFu);
-                const uint32_t row = PLAIN ? wd.base
+                const uint32_t row = PLAIN ? wd.base | (GLV && w >= NWIN_COMPACT ? PAY_ENDO : 0u)
                                    : COMPACT ? ((uint32_t)w % NWIN_WC * table_stride + wd.base) | (w >= NWIN_WC ? PAY_ENDO : 0u)
                                              : (uint32_t)w * table_stride + wd.base;
                 spay[pos] = (row + i) | (c & 0x80000000u);
@@ -1319,11 +1346,13 @@ __global__ void SRS_KERNEL_BOUNDS(PLAN_THREADS, 1)
     }
 }
 
-__global__ void k_link(const uint32_t *__restrict__ plan, size_t plan_stride, int nlevels, Link *__restrict__ link) {
+// `nseg`: the segments that k_plan ran for; the others (a plain key of form 2 populates 8 of the 16) own no part on any level, so that
+// base[l][nseg .. NSEG_W] all hold the number of parts and link_segment never names one of them
+__global__ void k_link(const uint32_t *__restrict__ plan, size_t plan_stride, int nlevels, Link *__restrict__ link, uint32_t nseg) {
     const uint32_t t = threadIdx.x;
     for (int l = 0; l < nlevels; ++l) {
         uint32_t c = 0;
-        if (t < NSEG_W) {
+        if (t < nseg) {
             const uint32_t *pl = plan + (size_t)t * plan_stride;
             if ((uint32_t)l < pl[plan_stride - 4]) c = pl[(size_t)(l + 1) * (NBUCKET + 1) + NBUCKET];
         }
@@ -1964,13 +1993,15 @@ void build_table(Key &k, hipStream_t stream) {
 
 int choose_windows(Key &k) {
     const int64_t mode = tuning::get_or(tuning::MSM_COMPACT, 0);
-    k.plain = tuning::get_or(tuning::MSM_PLAIN, 0) == 1;
+    const int64_t form = tuning::get_or(tuning::MSM_PLAIN, 0);
+    k.plain_form = (form == 1 || form == 2) ? (uint8_t)form : 0;
+    k.plain = k.plain_form != 0;
     if (k.plain && mode != 0) {
-        set_error("msm_plain = 1 and msm_compact = " + std::to_string(mode) + " are both set: a key is plain (the bases alone) or compact (8 windows), choose one");
+        set_error("msm_plain = " + std::to_string(form) + " and msm_compact = " + std::to_string(mode) + " are both set: a key is plain (the bases alone) or compact (8 windows), choose one");
         throw DeviceError{4};      // SRS_ERR_INVALID
     }
     if (k.plain && k.world > 1) {
-        set_error("plain key (msm_plain = 1): a key spread over " + std::to_string(k.world) + " ranks or devices is not supported");
+        set_error("plain key (msm_plain = " + std::to_string(form) + "): a key spread over " + std::to_string(k.world) + " ranks or devices is not supported");
         throw DeviceError{4};
     }
     if (k.plain) return 1;
@@ -2499,6 +2530,9 @@ static bool use_wide(const Key &k, uint32_t n_max, uint32_t batch) {
 // The flow of the 16 segments, shared by the wide windows and by plain keys: segment counts -> offsets -> grouping (the two passes of
 // `seg_count` / `seg_group` over the scalars), the counting sort inside the segments, level 0 over `table`, the levels and the bucket
 // reduction of the 16 segments as ONE linked batch -> `sums` partial sums per segment in b.d_seg.
+// `nseg`: the segments that can hold an entry, 0 .. nseg - 1 (a plain key of form 2: 8).  The plan, the maps, the wave-level pass and the
+// bucket reduction run for these alone.  The stages in front only see segments without entries: k_seg_scan gives them no tile (tile_base
+// and tile_base2 repeat the total, so link_segment stays below nseg) and k_link no part.
 template <class C>
 struct SegKernels {
     decltype(&k_seg_pass<C, false, false>) seg_count, seg_group;
@@ -2507,11 +2541,11 @@ struct SegKernels {
 };
 template <class C>
 static void segment_flow(const WideShape &w, const WideBufs &b, const WideDesc &wd, uint32_t table_stride, const SegKernels<C> &kn,
-                         const affine_t *table, uint32_t sums, hipStream_t stream) {
+                         const affine_t *table, uint32_t sums, hipStream_t stream, uint32_t nseg = NSEG_W) {
     uint32_t *seg_total = b.seg3, *seg_off = b.seg3 + (NSEG_W + 2), *tile_base = b.seg3 + 2 * (NSEG_W + 2), *tile_base2 = b.seg3 + 3 * (NSEG_W + 2);
     // sort: segment counts -> offsets -> grouping (MSD pass), then the counting sort inside the segments
     SRS_HIP_CHECK(hipMemsetAsync(seg_total, 0, (NSEG_W + 1) * sizeof(uint32_t), stream));
-    SRS_HIP_CHECK(hipMemsetAsync(b.count, 0, (size_t)NSEG_W * NBUCKET * sizeof(uint32_t), stream));
+    SRS_HIP_CHECK(hipMemsetAsync(b.count, 0, (size_t)nseg * NBUCKET * sizeof(uint32_t), stream));
     SRS_LAUNCH(kn.seg_count, (w.T), (WIDE_THREADS), 0, stream, wd, b.tile_cnt, w.T, seg_total, (uint16_t *)nullptr,
                (uint32_t *)nullptr, table_stride);
     const uint32_t small_tiles = (w.M >> 19) < 64 ? 1u : 0u, tile2_host = small_tiles ? SORT_TILE2 / 4 : SORT_TILE2;
@@ -2519,26 +2553,26 @@ static void segment_flow(const WideShape &w, const WideBufs &b, const WideDesc &
     SRS_LAUNCH(kn.seg_group, (w.T), (WIDE_THREADS), 0, stream, wd, b.tile_cnt, w.T, seg_total, b.gkey, b.gpay, table_stride);
     SRS_LAUNCH(k_hist_g, (w.tiles_g), (SORT_THREADS), 0, stream, (const uint16_t *)b.gkey, (const uint32_t *)seg_off,
                (const uint32_t *)tile_base, b.count, b.tile_hist);
-    SRS_LAUNCH(k_plan, (NSEG_W, w.levels + 1), (PLAN_THREADS), 0, stream, (const uint32_t *)b.count, b.cursor, b.plan, w.plan_stride, w.levels,
+    SRS_LAUNCH(k_plan, (nseg, w.levels + 1), (PLAN_THREADS), 0, stream, (const uint32_t *)b.count, b.cursor, b.plan, w.plan_stride, w.levels,
                w.l0_log, (uint32_t)ACC_L1_LOG, (const uint32_t *)seg_off);
-    SRS_LAUNCH(k_scan_seg_g, (SEG, NSEG_W), (1024), 0, stream, b.tile_hist, w.tiles_g, (const uint32_t *)tile_base, (const uint32_t *)b.plan,
+    SRS_LAUNCH(k_scan_seg_g, (SEG, nseg), (1024), 0, stream, b.tile_hist, w.tiles_g, (const uint32_t *)tile_base, (const uint32_t *)b.plan,
                w.plan_stride);
     SRS_LAUNCH(kn.group_g, (w.tiles_g), (SORT_THREADS), 0, stream, (const uint16_t *)b.gkey, (const uint32_t *)b.gpay, (const uint32_t *)seg_off,
                (const uint32_t *)tile_base, (const uint32_t *)b.tile_hist, b.gkey2, b.gpay2);
     // tiles of SORT_TILE2 entries cut per segment: at most M / SORT_TILE2 + NSEG_W of them; 8 x ceil(. / 8) workgroups (XCD mapping)
     SRS_LAUNCH(k_scatter2_g, (8 * ceil_div(ceil_div(w.M, tile2_host) + NSEG_W, 8)), (SORT_THREADS), 0, stream, (const uint16_t *)b.gkey2,
                (const uint32_t *)b.gpay2, (const uint32_t *)seg_off, (const uint32_t *)tile_base2, b.cursor, b.sorted);
-    SRS_LAUNCH(k_link, (1), (64), 0, stream, (const uint32_t *)b.plan, w.plan_stride, w.levels, b.link);
+    SRS_LAUNCH(k_link, (1), (64), 0, stream, (const uint32_t *)b.plan, w.plan_stride, w.levels, b.link, nseg);
     // from here on the 16 segments are ONE linked batch: no strides, the link says where a segment's parts start
     const Parts p{b.plan, w.plan_stride, b.ping, 0, b.pong, 0, b.link};
-    SRS_LAUNCH(k_expand, (NBUCKET / 4, NSEG_W), (256), 0, stream, p.plan, p.plan_stride, b.tb, (size_t)0, p.link, 1u);
+    SRS_LAUNCH(k_expand, (NBUCKET / 4, nseg), (256), 0, stream, p.plan, p.plan_stride, b.tb, (size_t)0, p.link, 1u);
     SRS_LAUNCH_TIMED("msm_accum0", wd.n, kn.accum0, (ceil_div(w.cap0, ACC_THREADS)), (ACC_THREADS), 0, stream, (const uint32_t *)b.sorted,
                      (size_t)0, p.plan, p.plan_stride, (const uint16_t *)b.tb, (size_t)0, table, p.ping, (size_t)0,
                      1u << w.l0_log, p.link);
-    accum_levels<C>(p, w, (uint64_t)NSEG_W * (NBUCKET + 1), 1, stream);
-    SRS_LAUNCH((k_accum_final<C>), (NBUCKET / (FINAL_THREADS / 64), NSEG_W), (FINAL_THREADS), 0, stream, (const xyzz_t *)p.ping, p.stride0,
+    accum_levels<C>(p, w, (uint64_t)nseg * (NBUCKET + 1), 1, stream);
+    SRS_LAUNCH((k_accum_final<C>), (NBUCKET / (FINAL_THREADS / 64), nseg), (FINAL_THREADS), 0, stream, (const xyzz_t *)p.ping, p.stride0,
                (const xyzz_t *)p.pong, p.stride1, p.plan, p.plan_stride, b.buckets, p.link);
-    reduce_buckets<C>(p, NSEG_W, b.buckets, 0, b.rc, sums, b.d_seg, stream);
+    reduce_buckets<C>(p, nseg, b.buckets, 0, b.rc, sums, b.d_seg, stream);
 }
 
 template <class C>
@@ -2561,7 +2595,12 @@ static bool enqueue_wide_t(Key &k, const fe_t *scalars_dev, uint32_t n, uint32_t
 // k_hist_g to reduce_buckets the 16 windows are the 16 linked segments -- every entry gathers from k.table, the bases.  What leaves is 3 partial sums
 // per window, landed at point 3 NWIN m of the slot; finish_t weights the windows.  MSM m of a batch is one such flow after the other on
 // the stream: they share the arena in stream order (the caller has reserved it for the largest of them).
+// Form 2 (msm_plain = 2, Key::plain_form): the same flow over the split scalar.  k_seg_pass<PLAIN, GLV> leaves 2 entries per scalar in
+// each of 8 windows, those of k2 flagged PAY_ENDO; level 0 is k_accum0c, which multiplies a flagged entry's x by beta; the stages from the
+// plan on run for 8 segments (segment_flow: nseg), 3 x 8 partial sums land and finish_t weights 8 windows.  A scalar has 16 digit rows in
+// either form, so the shape, the buffers and workspace_bytes_plain are those of form 1.
 static WideShape plain_shape(uint32_t n) { return wide_shape(n, NWIN); }
+static int plain_windows(int form) { return form == 2 ? NWIN_COMPACT : NWIN; }
 // what the flows of up to n_max scalars need.  The layout grows with n while the part length stays (wide_shape), but a longer part shrinks
 // ping / pong: the largest n of every shorter part length is a candidate too, so that a smaller MSM later on the stream never grows the arena
 static size_t workspace_bytes_plain(uint32_t n_max) {
@@ -2583,11 +2622,14 @@ template <class C>
 static void enqueue_plain_t(Key &k, const fe_t *scalars_dev, uint32_t n, uint32_t base, int is_mont, hipStream_t stream, uint32_t slot,
                             uint32_t m) {
     const WideShape w = plain_shape(n);
-    const SegKernels<C> kn{&k_seg_pass<C, false, false, true>, &k_seg_pass<C, true, false, true>, &k_group_g<false>, &k_accum0<C>};
+    const SegKernels<C> kn = k.plain_form == 2
+        ? SegKernels<C>{&k_seg_pass<C, false, false, true, true>, &k_seg_pass<C, true, false, true, true>, &k_group_g<false>, &k_accum0c<C>}
+        : SegKernels<C>{&k_seg_pass<C, false, false, true>, &k_seg_pass<C, true, false, true>, &k_group_g<false>, &k_accum0<C>};
     const WideBufs b = carve(k.arena, [&](auto &A) { return wide_layout(A, w); });
     const WideDesc wd{scalars_dev, n, base, 0u, 1u, is_mont};            // a plain key is never sharded (choose_windows)
-    segment_flow<C>(w, b, wd, 0u, kn, k.table, 3, stream);
-    land(k, b.d_seg, 3 * (size_t)NWIN, slot, stream, 3 * (size_t)NWIN * m);
+    const uint32_t nwin = (uint32_t)plain_windows(k.plain_form);
+    segment_flow<C>(w, b, wd, 0u, kn, k.table, 3, stream, nwin);
+    land(k, b.d_seg, 3 * (size_t)nwin, slot, stream, 3 * (size_t)NWIN * m);     // (the slot keeps room for 16 windows per MSM in either form)
 }
 
 // a set of <= BATCH_ARGS MSMs on a plain key.  Returns false when every MSM is empty (nothing was launched).
@@ -2605,6 +2647,7 @@ static bool enqueue_plain_set_t(Key &k, const fe_t *const *scalars_dev, const ui
     }
     k.landing[slot].wide = false;
     k.landing[slot].plain = true;
+    k.landing[slot].plain_form = k.plain_form;
     k.landing[slot].plain_ran = ran;
     return true;
 }
@@ -2622,8 +2665,10 @@ static void finish_t(Key &k, uint32_t batch, uint32_t slot, bool launched, xyzz_
     fe_t c = F::one();
     for (int d = 0; d < 5; ++d) c = F::halve(c);
     const bool plain = k.landing[slot].plain;
+    const int nwin = plain_windows(plain ? k.landing[slot].plain_form : 0);    // windows a plain flow landed per MSM
     std::vector<xyzz_t> two(plain ? 3 * (size_t)NWIN * batch : 3 * (size_t)batch + (k.landing[slot].wide ? 1 : 0));
     for (size_t i = 0; i < two.size(); ++i) {
+        if (plain && (i / 3) % NWIN >= (size_t)nwin) continue;  // form 2 lands 8 of the 16 windows an MSM has room for
         two[i].x = F::mul(raw[i].x, c);
         two[i].y = F::mul(raw[i].y, c);
         two[i].zz = F::mul(raw[i].zz, c);
@@ -2635,10 +2680,10 @@ static void finish_t(Key &k, uint32_t batch, uint32_t slot, bool launched, xyzz_
         return Ec<C>::add(a, two[at + 1]);
     };
     if (plain) {                                                // sum_w 2^(16 w) R_w as a Horner chain from the top window: 240 doublings, 15 additions
-        for (uint32_t m = 0; m < batch; ++m) {
+        for (uint32_t m = 0; m < batch; ++m) {                  // (form 2: 8 windows, 112 doublings, 8 additions)
             xyzz_t acc = Ec<C>::identity();
-            for (int w = NWIN - 1; w >= 0 && (k.landing[slot].plain_ran >> m & 1u); --w) {
-                for (int d = 0; d < WBITS && w != NWIN - 1; ++d) acc = Ec<C>::dbl(acc);
+            for (int w = nwin - 1; w >= 0 && (k.landing[slot].plain_ran >> m & 1u); --w) {
+                for (int d = 0; d < WBITS && w != nwin - 1; ++d) acc = Ec<C>::dbl(acc);
                 acc = Ec<C>::add(acc, bucket_sum(3 * ((size_t)NWIN * m + w)));
             }
             result_host[m] = acc;

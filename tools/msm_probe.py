@@ -1,6 +1,6 @@
 """Wall time of ck.commit on device-resident scalars over a range of sizes (one key of 2^24 bases); run once per setting of the
 tunables (SRS_TEST_TUNING="msm_sort=2,..." of the Python mirror: the key is created under them, so msm_compact / msm_plain choose its
-form).  usage: python tools/msm_probe.py [log_key] [sizes...] [--setup] [--spread] [--batch COUNT N] [--streamed N]
+form; the set-up line prints plain=0 / 1 / 2, the plain form).  usage: python tools/msm_probe.py [log_key] [sizes...] [--setup] [--spread] [--batch COUNT N] [--streamed N]
   --setup          also print the key's set-up time and srs_ck_table_bytes
   --spread         print min - max over the repeats instead of their mean (one synchronised call per repeat)
   --batch C N      then a commit_batch of C vectors of N uniform scalars
@@ -57,7 +57,7 @@ ck = S.CommitmentKey.setup_synthetic(0, 1 << log_key, seed=3)
 torch.cuda.synchronize()
 if setup is not None:
     print(f"key_setup 2^{log_key}: {time.perf_counter() - t0:6.3f} s  table_bytes={ck.table_bytes()} ({ck.table_bytes() / 2**30:.2f} GiB) "
-          f"plain={int(ck.is_plain())} compact={int(ck.is_compact())} wide_table={int(ck.has_wide_table())}  tag={tag}", flush=True)
+          f"plain={ck.plain_form()} compact={int(ck.is_compact())} wide_table={int(ck.has_wide_table())}  tag={tag}", flush=True)
 g = torch.Generator(device="cuda").manual_seed(1)
 
 
