@@ -75,7 +75,7 @@ const char *srs_version(void);
  * "msm_plain" = 1 for a key that is its bases alone (no window table: 1/16 of the HBM, no set-up, more work per MSM; srs_ck_is_plain), or
  * "msm_plain" = 2 for the same key whose MSMs take 8 windows through the endomorphism instead of 16.
  * Names (srs_tuning_name(i), i = 0, 1, ... until NULL): msm_sort, msm_l0, msm_wide, msm_wide_min, msm_slots, msm_slot_log,
- * msm_expect_ovf, msm_quad_max, commit_chunks, pg_f_eval, pg_g_fft, jit_always, no_jit, msm_compact, pg_compat_tree, pg_jit_force, pg_jit_waves, msm_plain.  Process-wide; set before the calls they
+ * msm_expect_ovf, msm_quad_max, commit_chunks, pg_f_eval, pg_g_fft, jit_always, no_jit, msm_compact, pg_compat_tree, pg_jit_force, pg_jit_waves, msm_plain, msm_plain_fold.  Process-wide; set before the calls they
  * affect (a value is read when a call starts).  rc SRS_ERR_INVALID for an unknown name.  No reference counterpart. */
 int srs_tuning_set(const char *name, int64_t value);
 int srs_tuning_get(const char *name, int64_t *value);        /* *value = INT64_MIN while unset */
@@ -215,7 +215,12 @@ size_t srs_ck_table_bytes(const srs_ck *ck);
  * bases and nothing else -- 64 bytes per base, no window expansion at creation.  Every MSM over it, of any size, recodes the scalars into
  * 16 signed 16-bit digits, groups them by window, accumulates the 16 windows' buckets from the bases and weights window w by 2^(16 w)
  * with 240 doublings at its end: the same additions per scalar as a full key, plus 16 bucket reductions per MSM, so small MSMs are
- * slower (README).  Same entries, same results bit for bit; a streamed commit runs every chunk as a whole MSM.
+ * slower (README).  Same entries, same results bit for bit.  A streamed commit (srs_commit_upload,
+ * srs_commit_upload_columns, srs_run_sps_protocol) adds every chunk's finished buckets into one running bucket set per window -- run
+ * state of the key, 64 MiB ("msm_plain" = 2: 32 MiB), allocated at the first such commit, not counted by srs_ck_table_bytes -- and
+ * reduces, lands and weights the windows once per commit; grouping, plans and accumulation levels stay per chunk.  Measured on the
+ * k = 20 witness (12 * 2^20 scalars, profiles/plain_fold_ab.txt): 14.4-14.5 ms against 16.6-16.8 ms with every chunk a whole MSM
+ * ("msm_plain" = 2: 12.2-12.6 against 14.0-14.2 ms); tunable "msm_plain_fold" = 0, read when a streamed commit starts, keeps the latter.
  * "msm_plain" = 2 is the same key in memory (64 bytes per base, no window expansion) whose MSMs split the scalar as a compact key does,
  * k = k1 + lambda k2: 8 signed 16-bit digits of k1 and 8 of k2, digit w of either in window w, the entries of k2 gathering
  * phi(P) = (beta x, y) from the same base for one field product.  8 bucket reductions and 112 doublings per MSM instead of 16 and 240: the
@@ -224,6 +229,10 @@ size_t srs_ck_table_bytes(const srs_ck *ck);
  * spread over ranks or devices (world > 1; srs_ck_create_multi / srs_ck_setup_synthetic_multi over more than one device).
  * srs_ck_is_plain: the form, 1 or 2, of a plain key; 0 for every other key.  No reference counterpart. */
 int srs_ck_is_plain(const srs_ck *ck);
+/* Diagnostics of the plain flow (host-only query, no reference counterpart): out[0] = sets of streamed commits that added their buckets
+ * into the running buckets (first and last set included), out[1] = bucket reductions of the plain flow -- one per unfolded MSM, one per
+ * folded commit.  Both 0 on a key that is not plain.  A multi-device key of one shard reports its shard. */
+int srs_ck_plain_stats(const srs_ck *ck, uint64_t *out2);
 /* Host-only diagnostics of the split (no device needed, no reference counterpart).  srs_glv_constants: lambda (scalar field) and
  * beta (base field) of `curve` as canonical integers, 4 x u64 little-endian.  srs_glv_decompose: k (repr as elsewhere) ->
  * |k1|, |k2| (canonical integers) and their signs (1 = negative), by the very body the digit kernel runs:

@@ -143,6 +143,14 @@ class CommitmentKey:
         scalar (msm_plain=2, the endomorphism).  The value of srs_ck_is_plain."""
         return int(L.lib().srs_ck_is_plain(self._h))
 
+    def plain_stats(self):
+        """Diagnostics of the plain flow (srs_ck_plain_stats): dict(fold_sets, reductions) -- sets of streamed commits that added their
+        buckets into the key's running buckets, and bucket reductions (one per unfolded MSM, one per folded commit).  Zeros on a key that
+        is not plain."""
+        out = (C.c_uint64 * 2)()
+        L.check(L.lib().srs_ck_plain_stats(self._h, out))
+        return dict(fold_sets=int(out[0]), reductions=int(out[1]))
+
     def table_bytes(self):
         """Bytes of window tables this key holds on its device(s) (srs_ck_table_bytes): 64 per base and window -- 16 (+ 13 wide) windows on a
         full key, 8 (+ 7 wide under msm_compact=2) on a compact one, 1 (the bases) on a plain one."""

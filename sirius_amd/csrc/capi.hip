@@ -938,6 +938,17 @@ int srs_ck_msm_stats(const srs_ck *ck, uint64_t *out) {
     return SRS_OK;
 }
 
+int srs_ck_plain_stats(const srs_ck *ck, uint64_t *out) {
+    if (!ck || !out) return fail(SRS_ERR_INVALID, "srs_ck_plain_stats: bad argument");
+    out[0] = out[1] = 0;
+    for_each_key(ck, [&](const msm::Key &k, const CkShard *) {      // (a plain key is one key: a handle's own, or the one shard of a multi-device handle)
+        if (!k.plain) return;
+        out[0] += k.stat_plain_fold_sets;
+        out[1] += k.stat_plain_reductions;
+    });
+    return SRS_OK;
+}
+
 int srs_ck_shard_stats(const srs_ck *ck, int shard, uint64_t *out) {
     if (!ck || !out || shard < 0) return fail(SRS_ERR_INVALID, "srs_ck_shard_stats: bad argument");
     for (int i = 0; i < 4; ++i) out[i] = 0;
@@ -1184,9 +1195,10 @@ int commit_streamed_core(StreamRes ck_, const std::vector<Seg> &segs, size_t n, 
     SRS_HIP_CHECK(hipEventRecord(ck->events[chunks], st));
     SRS_HIP_CHECK(hipStreamWaitEvent(ck->copy_stream, ck->events[chunks], 0));
     std::vector<bool> launched(sets, false);
-    // every chunk on the 16-bit windows: the chunks fold their buckets into one running set and only the last one is reduced.  A plain key has
-    // no running buckets (msm.h): every chunk is a whole MSM over its base range, still behind its own upload, and the results are added below
-    bool fold = sets > 1 && !ck->key.plain;
+    // every chunk on the 16-bit windows: the chunks fold their buckets into one running set and only the last one is reduced.  A plain key
+    // keeps one running set per window (msm.h) and folds the same way; under tuning msm_plain_fold = 0 (read here, per commit) every chunk
+    // is a whole MSM over its base range, still behind its own upload, and the results are added below.  A folded commit has no empty set
+    bool fold = sets > 1 && (!ck->key.plain || tuning::get_or(tuning::MSM_PLAIN_FOLD, 1) != 0);
     for (size_t j = 0; j < chunks; ++j) fold = fold && sp.count(cut[j], cut[j + 1]) > 0;
     for (size_t t = 0; t < tails; ++t) fold = fold && tail->cut[t + 1] > tail->cut[t];
     auto fold_of = [&](size_t j) { return !fold ? msm::FOLD_NONE : (j == 0 ? msm::FOLD_FIRST : (j + 1 == sets ? msm::FOLD_LAST : msm::FOLD_MIDDLE)); };

@@ -74,8 +74,9 @@ inline bool expect_ovf_initial() { return tuning::get_or(tuning::MSM_EXPECT_OVF,
 // msm_compact = 1 never has one.
 // A PLAIN key (tuning msm_plain = 1 at creation) holds window 0 alone: table[i] = P_i, 64 bytes per base.  An MSM over it groups its
 // signed 16-bit digits by WINDOW (the plain flow, msm.hip), runs the 16 windows as 16 linked bucket sets that all gather from that one
-// window, and finish() weights window w by 2^(16 w) with a Horner chain of doublings.  No table_w, no slot mode, no fold, no hot-bucket
-// prediction; single-rank keys only (capi.hip refuses the rest).
+// window, and finish() weights window w by 2^(16 w) with a Horner chain of doublings.  No table_w, no slot mode, no hot-bucket
+// prediction; single-rank keys only (capi.hip refuses the rest).  The sets of a chunked commit fold (enqueue(.., fold)) into one running
+// bucket set PER WINDOW, [windows][NBUCKET] points of run state (fold_buckets: 64 MiB, form 2: 32 MiB, allocated at the first folded set).
 // Form 2 (msm_plain = 2) is the same key in memory; its MSMs split the scalar as a compact key does (k = k1 + lambda k2, glv.cuh) and run 8
 // windows of two entries per scalar -- those of k2 flagged PAY_ENDO, level 0 gathers phi of the base -- so 8 bucket sets and 112 doublings.
 struct Key {
@@ -91,6 +92,9 @@ struct Key {
     affine_t *table = nullptr;
     affine_t *table_w = nullptr;   // T_w[w][i] = 2^(20 w) P_i, w < NWIN_W -- w < NWIN_WC on a compact key (keys of >= 2^WIDE_MIN_KEY_LOG bases; owned by the key: release())
     uint64_t stat_slot_sets = 0, stat_hot_sets = 0, stat_redo = 0, stat_other_sets = 0;   // srs_ck_msm_stats
+    // srs_ck_plain_stats (plain keys): sets that added their buckets into the running buckets (first and last included), and bucket
+    // reductions of the plain flow -- one per unfolded MSM, one per folded commit
+    uint64_t stat_plain_fold_sets = 0, stat_plain_reductions = 0;
     uint64_t last_entries = 0;        // non-zero digits (= bucket additions) of the last commit that ran in slot mode (note_commit) ...
     uint64_t last_scalars = 0;        // ... and its scalars (both set by note_commit, both 0 when the commit had no slot-mode set): the density the next streamed commit's chunk cuts are chosen for
 
@@ -102,7 +106,10 @@ struct Key {
     // it (3 sums per WINDOW of every MSM, 16 or with plain_form == 2 eight of them, finish() weights the windows) for the MSMs of the mask --
     // the others were empty
     struct Landing { bool wide = false, slot_mode = false, ovf_on = false; uint32_t batch = 0; bool plain = false; uint8_t plain_form = 0; uint32_t plain_ran = 0; } landing[LANDING_SLOTS];
-    xyzz_t *fold_buckets = nullptr;   // running bucket sums of a chunked commit (enqueue(.., fold)) outside slot mode
+    // running bucket sums of a chunked commit (enqueue(.., fold)) outside slot mode: [NBUCKET] points (enqueue_t), or on a plain key
+    // [windows][NBUCKET] (the plain flow).  A plain key never takes enqueue_t and no other key the plain flow, so the two uses of the
+    // pointer cannot meet.  Run state, not table: table_bytes() does not count it.
+    xyzz_t *fold_buckets = nullptr;
     // slot mode (see SLOT_LOG), grow-only
     xyzz_t *slots = nullptr;          // [batch][NBUCKET][S] persistent partial sums of the running commit
     size_t slots_pts = 0;
@@ -150,8 +157,12 @@ void run(Key &k, const fe_t *const *scalars_dev, const uint32_t *n_host, uint32_
 // `fold`: the sets of a chunked commit share ONE bucket set (the buckets are the digit values, whatever the base offset), and the
 // bucket reduction is linear: a set with FOLD_FIRST / FOLD_MIDDLE only adds its bucket sums into the key's running buckets (no
 // reduction, no result), the FOLD_LAST set adds its own and reduces the total -- one k_rowcol + k_reduce_final + host finish per commit
-// instead of one per chunk.  batch == 1, 16-bit-window sets only (a chunked commit never takes the wide windows).  A plain key has no
-// running buckets: its callers pass FOLD_NONE for every chunk and add the chunks' results.
+// instead of one per chunk.  batch == 1, 16-bit-window sets only (a chunked commit never takes the wide windows).  On a plain key the
+// bucket of an entry is (window, |digit|) and the window weights are linear too: a folded set runs the plain flow up to its finished
+// buckets and adds those of every window into the running buckets of that window (FOLD_FIRST overwrites them: nothing of an earlier or
+// failed commit leaks in), FOLD_LAST reduces the windows' totals and lands 3 sums per window -- the reductions of the 16 (8) windows, the
+// landing copy and the host's chain of doublings once per commit; grouping, plans, levels and the wave-level pass stay per set.  No set
+// of such a commit may be empty.  Callers that pass FOLD_NONE for every chunk (tuning msm_plain_fold = 0) add the chunks' results.
 enum Fold { FOLD_NONE = 0, FOLD_FIRST = 1, FOLD_MIDDLE = 2, FOLD_LAST = 3 };
 bool enqueue(Key &k, const fe_t *const *scalars_dev, const uint32_t *n_host, const uint32_t *base_host, uint32_t batch, int is_mont,
              hipStream_t stream, uint32_t slot, Fold fold = FOLD_NONE);

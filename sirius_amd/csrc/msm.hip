@@ -1737,6 +1737,28 @@ __global__ void SRS_KERNEL_BOUNDS(64, 1)
     }
 }
 
+// the same for the linked segments of the plain flow (one segment = one window of a plain key): segment m's finished buckets, exactly where
+// k_rowcol finds them with from_buckets == 0 -- buckets + m NBUCKET when the wave-level pass wrote them, ping / pong at the segment's LINKED
+// offset when its plan header says every bucket was single (every small chunk) -- go into total[m][NBUCKET].
+// grid = (NBUCKET / 64, segments)
+template <class C>
+__global__ void SRS_KERNEL_BOUNDS(64, 1)
+    k_bucket_fold_seg(const xyzz_t *__restrict__ buckets, const xyzz_t *__restrict__ ping, const xyzz_t *__restrict__ pong,
+                      const uint32_t *__restrict__ plan, size_t plan_stride, const Link *__restrict__ link, xyzz_t *__restrict__ total,
+                      int first) {
+    using E29 = Ec29<C>;
+    const uint32_t m = blockIdx.y, b = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t *hdr = plan + (size_t)m * plan_stride + plan_stride - 4;   // [0] levels run, [1] all buckets single
+    const xyzz_t *B = hdr[1] ? ((hdr[0] & 1u) ? ping + (size_t)link->base[0][m] : pong + (size_t)link->base[1][m])
+                             : buckets + (size_t)m * NBUCKET;
+    xyzz_t *T = total + (size_t)m * NBUCKET;
+    if (first) {
+        T[b] = B[b];
+    } else {
+        T[b] = E29::pack(E29::add(E29::unpack(T[b]), E29::unpack(B[b])));
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // 5. bucket reduction  S = sum_b (b+1) B_b,  b = hi * RED_COLS + lo
 //    S = RED_COLS * sum_hi hi * R_hi  +  sum_lo (lo+1) * C_lo
@@ -2533,6 +2555,8 @@ static bool use_wide(const Key &k, uint32_t n_max, uint32_t batch) {
 // `nseg`: the segments that can hold an entry, 0 .. nseg - 1 (a plain key of form 2: 8).  The plan, the maps, the wave-level pass and the
 // bucket reduction run for these alone.  The stages in front only see segments without entries: k_seg_scan gives them no tile (tile_base
 // and tile_base2 repeat the total, so link_segment stays below nseg) and k_link no part.
+// `reduce` = false stops behind k_accum_final (a folded set of a plain key: its buckets go into the key's running buckets instead); the
+// parts of the linked batch are returned for whoever goes on.
 template <class C>
 struct SegKernels {
     decltype(&k_seg_pass<C, false, false>) seg_count, seg_group;
@@ -2540,8 +2564,8 @@ struct SegKernels {
     decltype(&k_accum0<C>) accum0;
 };
 template <class C>
-static void segment_flow(const WideShape &w, const WideBufs &b, const WideDesc &wd, uint32_t table_stride, const SegKernels<C> &kn,
-                         const affine_t *table, uint32_t sums, hipStream_t stream, uint32_t nseg = NSEG_W) {
+static Parts segment_flow(const WideShape &w, const WideBufs &b, const WideDesc &wd, uint32_t table_stride, const SegKernels<C> &kn,
+                          const affine_t *table, uint32_t sums, hipStream_t stream, uint32_t nseg = NSEG_W, bool reduce = true) {
     uint32_t *seg_total = b.seg3, *seg_off = b.seg3 + (NSEG_W + 2), *tile_base = b.seg3 + 2 * (NSEG_W + 2), *tile_base2 = b.seg3 + 3 * (NSEG_W + 2);
     // sort: segment counts -> offsets -> grouping (MSD pass), then the counting sort inside the segments
     SRS_HIP_CHECK(hipMemsetAsync(seg_total, 0, (NSEG_W + 1) * sizeof(uint32_t), stream));
@@ -2572,7 +2596,8 @@ static void segment_flow(const WideShape &w, const WideBufs &b, const WideDesc &
     accum_levels<C>(p, w, (uint64_t)nseg * (NBUCKET + 1), 1, stream);
     SRS_LAUNCH((k_accum_final<C>), (NBUCKET / (FINAL_THREADS / 64), nseg), (FINAL_THREADS), 0, stream, (const xyzz_t *)p.ping, p.stride0,
                (const xyzz_t *)p.pong, p.stride1, p.plan, p.plan_stride, b.buckets, p.link);
-    reduce_buckets<C>(p, nseg, b.buckets, 0, b.rc, sums, b.d_seg, stream);
+    if (reduce) reduce_buckets<C>(p, nseg, b.buckets, 0, b.rc, sums, b.d_seg, stream);
+    return p;
 }
 
 template <class C>
@@ -2620,7 +2645,7 @@ static size_t workspace_bytes_plain(uint32_t n_max) {
 
 template <class C>
 static void enqueue_plain_t(Key &k, const fe_t *scalars_dev, uint32_t n, uint32_t base, int is_mont, hipStream_t stream, uint32_t slot,
-                            uint32_t m) {
+                            uint32_t m, Fold fold = FOLD_NONE) {
     const WideShape w = plain_shape(n);
     const SegKernels<C> kn = k.plain_form == 2
         ? SegKernels<C>{&k_seg_pass<C, false, false, true, true>, &k_seg_pass<C, true, false, true, true>, &k_group_g<false>, &k_accum0c<C>}
@@ -2628,21 +2653,34 @@ static void enqueue_plain_t(Key &k, const fe_t *scalars_dev, uint32_t n, uint32_
     const WideBufs b = carve(k.arena, [&](auto &A) { return wide_layout(A, w); });
     const WideDesc wd{scalars_dev, n, base, 0u, 1u, is_mont};            // a plain key is never sharded (choose_windows)
     const uint32_t nwin = (uint32_t)plain_windows(k.plain_form);
+    if (fold != FOLD_NONE) {                                             // a set of a chunked commit: the window is the bucket set, whatever the base offset
+        const Parts p = segment_flow<C>(w, b, wd, 0u, kn, k.table, 3, stream, nwin, false);
+        if (!k.fold_buckets) SRS_HIP_CHECK(hipMalloc((void **)&k.fold_buckets, (size_t)nwin * NBUCKET * sizeof(xyzz_t)));
+        SRS_LAUNCH((k_bucket_fold_seg<C>), (NBUCKET / 64, nwin), (64), 0, stream, (const xyzz_t *)b.buckets, (const xyzz_t *)p.ping,
+                   (const xyzz_t *)p.pong, p.plan, p.plan_stride, p.link, k.fold_buckets, fold == FOLD_FIRST ? 1 : 0);
+        ++k.stat_plain_fold_sets;
+        if (fold != FOLD_LAST) return;                                   // no reduction, no result for this set
+        reduce_buckets<C>(p, nwin, k.fold_buckets, 1, b.rc, 3, b.d_seg, stream);
+        ++k.stat_plain_reductions;
+        land(k, b.d_seg, 3 * (size_t)nwin, slot, stream);
+        return;
+    }
     segment_flow<C>(w, b, wd, 0u, kn, k.table, 3, stream, nwin);
+    ++k.stat_plain_reductions;
     land(k, b.d_seg, 3 * (size_t)nwin, slot, stream, 3 * (size_t)NWIN * m);     // (the slot keeps room for 16 windows per MSM in either form)
 }
 
 // a set of <= BATCH_ARGS MSMs on a plain key.  Returns false when every MSM is empty (nothing was launched).
 template <class C>
 static bool enqueue_plain_set_t(Key &k, const fe_t *const *scalars_dev, const uint32_t *n_host, const uint32_t *base_host, uint32_t batch,
-                                int is_mont, hipStream_t stream, uint32_t slot) {
+                                int is_mont, hipStream_t stream, uint32_t slot, Fold fold) {
     uint32_t n_max = 0, ran = 0;
     for (uint32_t m = 0; m < batch; ++m) n_max = std::max(n_max, n_host[m]);
     if (n_max == 0) return false;
     k.arena.reserve(workspace_bytes_plain(n_max));          // before the first launch: growing it between two flows would free memory in use
     for (uint32_t m = 0; m < batch; ++m) {
         if (n_host[m] == 0) continue;
-        enqueue_plain_t<C>(k, scalars_dev[m], n_host[m], base_host ? base_host[m] : 0u, is_mont, stream, slot, m);
+        enqueue_plain_t<C>(k, scalars_dev[m], n_host[m], base_host ? base_host[m] : 0u, is_mont, stream, slot, m, fold);
         ran |= 1u << m;
     }
     k.landing[slot].wide = false;
@@ -2708,15 +2746,15 @@ bool enqueue(Key &k, const fe_t *const *scalars_dev, const uint32_t *n_host, con
         set_error("internal: msm::enqueue fold needs one MSM per set");
         throw DeviceError{5};
     }
-    if (k.plain) {                           // every set, whatever its size: no slot mode, no fold, no wide table
-        if (fold != FOLD_NONE) {
-            set_error("internal: msm::enqueue fold on a plain key");
+    if (k.plain) {                           // every set, whatever its size: no slot mode, no wide table; a folded set adds into the running buckets
+        if (fold != FOLD_NONE && n_host[0] == 0) {       // (its commit's result is the LAST set's: no set of it may drop out)
+            set_error("internal: msm::enqueue empty folded set on a plain key");
             throw DeviceError{5};
         }
         k.landing[slot].slot_mode = false;
         ++k.stat_other_sets;
-        return k.curve == 0 ? enqueue_plain_set_t<Bn256>(k, scalars_dev, n_host, base_host, batch, is_mont, stream, slot)
-                            : enqueue_plain_set_t<Grumpkin>(k, scalars_dev, n_host, base_host, batch, is_mont, stream, slot);
+        return k.curve == 0 ? enqueue_plain_set_t<Bn256>(k, scalars_dev, n_host, base_host, batch, is_mont, stream, slot, fold)
+                            : enqueue_plain_set_t<Grumpkin>(k, scalars_dev, n_host, base_host, batch, is_mont, stream, slot, fold);
     }
     if (batch == 1 && fold == FOLD_NONE && use_wide(k, n_host[0], 1)) {      // the sets of a chunked commit stay on the 16-bit windows
         const uint32_t base = base_host ? base_host[0] : 0;

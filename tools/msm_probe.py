@@ -87,4 +87,4 @@ if streamed:
     hb.array[:] = trace_like(np.random.default_rng(1), n)
     d = torch.zeros((n, 4), dtype=torch.int64, device="cuda")
     txt, _ = timed(lambda: ck.commit_upload(hb.array, dev_copy=d))
-    print(f"streamed commit n={n} {txt}  point={ck.commit_upload(hb.array, dev_copy=d).tobytes().hex()[:16]}  {ck.msm_stats()}  tag={tag}", flush=True)
+    print(f"streamed commit n={n} {txt}  point={ck.commit_upload(hb.array, dev_copy=d).tobytes().hex()[:16]}  {ck.msm_stats()}  {ck.plain_stats()}  tag={tag}", flush=True)
