@@ -75,7 +75,7 @@ const char *srs_version(void);
  * "msm_plain" = 1 for a key that is its bases alone (no window table: 1/16 of the HBM, no set-up, more work per MSM; srs_ck_is_plain), or
  * "msm_plain" = 2 for the same key whose MSMs take 8 windows through the endomorphism instead of 16.
  * Names (srs_tuning_name(i), i = 0, 1, ... until NULL): msm_sort, msm_l0, msm_wide, msm_wide_min, msm_slots, msm_slot_log,
- * msm_expect_ovf, msm_quad_max, commit_chunks, pg_f_eval, pg_g_fft, jit_always, no_jit, msm_compact, pg_compat_tree, pg_jit_force, pg_jit_waves, msm_plain, msm_plain_fold.  Process-wide; set before the calls they
+ * msm_expect_ovf, msm_quad_max, commit_chunks, pg_f_eval, pg_g_fft, jit_always, no_jit, msm_compact, pg_compat_tree, pg_jit_force, pg_jit_waves, msm_plain, msm_plain_fold, msm_plain_batch.  Process-wide; set before the calls they
  * affect (a value is read when a call starts).  rc SRS_ERR_INVALID for an unknown name.  No reference counterpart. */
 int srs_tuning_set(const char *name, int64_t value);
 int srs_tuning_get(const char *name, int64_t *value);        /* *value = INT64_MIN while unset */
@@ -225,6 +225,14 @@ size_t srs_ck_table_bytes(const srs_ck *ck);
  * k = k1 + lambda k2: 8 signed 16-bit digits of k1 and 8 of k2, digit w of either in window w, the entries of k2 gathering
  * phi(P) = (beta x, y) from the same base for one field product.  8 bucket reductions and 112 doublings per MSM instead of 16 and 240: the
  * smaller fixed cost per MSM, for one more product per entry of k2 (INTEGRATION.md 4c says which form to choose when).
+ * srs_commit_batch and what is built on it (srs_commit_cross_terms, srs_sangria_prove, srs_sangria_prove_incoming,
+ * srs_is_sat_witness_commit) run two or more non-empty vectors (at most 16 per set) as ONE linked flow whose bucket sets are the
+ * (vector, window) pairs -- one set of launches, one bucket reduction and one landing copy per set, the vectors' chains of doublings
+ * over the library's host workers: 5 x 2^15 uniform scalars take 3.82-3.90 ms against 4.67-4.80 ms one after the other ("msm_plain" = 2:
+ * 2.92-2.99 against 3.75-3.79 ms; a default key: 0.75-0.79 ms; profiles/plain_batch_ab.txt).  The flow's workspace, about 13 MiB per
+ * (vector, window) pair -- 1.0 GiB for 5 vectors, 3.4 GiB for 16 ("msm_plain" = 2: half) -- is run state in the key's grow-only arena,
+ * not counted by srs_ck_table_bytes.  Tunable "msm_plain_batch" = 0, read per set, runs the vectors one after the other as before, without
+ * that workspace; so do sets with a vector above 2^20 scalars.
  * Refused with SRS_ERR_INVALID (srs_last_error names the tunables): "msm_plain" = 1 or 2 together with "msm_compact" != 0, and a plain key
  * spread over ranks or devices (world > 1; srs_ck_create_multi / srs_ck_setup_synthetic_multi over more than one device).
  * srs_ck_is_plain: the form, 1 or 2, of a plain key; 0 for every other key.  No reference counterpart. */
@@ -233,6 +241,10 @@ int srs_ck_is_plain(const srs_ck *ck);
  * into the running buckets (first and last set included), out[1] = bucket reductions of the plain flow -- one per unfolded MSM, one per
  * folded commit.  Both 0 on a key that is not plain.  A multi-device key of one shard reports its shard. */
 int srs_ck_plain_stats(const srs_ck *ck, uint64_t *out2);
+/* Diagnostics of the batched plain flow (host-only query, no reference counterpart): out[0] = sets of two or more non-empty MSMs that
+ * ran as one linked flow (tunable "msm_plain_batch", default 1), out[1] = the MSMs those sets carried.  Both 0 on a key that is not
+ * plain.  srs_ck_plain_stats and srs_ck_msm_stats count such a set as they count its members run one after the other. */
+int srs_ck_plain_batch_stats(const srs_ck *ck, uint64_t *out2);
 /* Host-only diagnostics of the split (no device needed, no reference counterpart).  srs_glv_constants: lambda (scalar field) and
  * beta (base field) of `curve` as canonical integers, 4 x u64 little-endian.  srs_glv_decompose: k (repr as elsewhere) ->
  * |k1|, |k2| (canonical integers) and their signs (1 = negative), by the very body the digit kernel runs:

@@ -56,6 +56,7 @@ def _prototypes():
         "srs_ck_is_compact": (i32, [vp]),
         "srs_ck_is_plain": (i32, [vp]),
         "srs_ck_plain_stats": (i32, [vp, C.POINTER(C.c_uint64)]),
+        "srs_ck_plain_batch_stats": (i32, [vp, C.POINTER(C.c_uint64)]),
         "srs_ck_table_bytes": (sz, [vp]),
         "srs_glv_constants": (i32, [i32, vp, vp]),
         "srs_glv_decompose": (i32, [i32, vp, i32, vp, vp, C.POINTER(i32), C.POINTER(i32)]),

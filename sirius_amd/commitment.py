@@ -151,6 +151,13 @@ class CommitmentKey:
         L.check(L.lib().srs_ck_plain_stats(self._h, out))
         return dict(fold_sets=int(out[0]), reductions=int(out[1]))
 
+    def plain_batch_stats(self):
+        """Diagnostics of the batched plain flow (srs_ck_plain_batch_stats): dict(sets, msms) -- sets of two or more non-empty MSMs that ran
+        as one linked flow (tuning msm_plain_batch, default 1), and the MSMs they carried.  Zeros on a key that is not plain."""
+        out = (C.c_uint64 * 2)()
+        L.check(L.lib().srs_ck_plain_batch_stats(self._h, out))
+        return dict(sets=int(out[0]), msms=int(out[1]))
+
     def table_bytes(self):
         """Bytes of window tables this key holds on its device(s) (srs_ck_table_bytes): 64 per base and window -- 16 (+ 13 wide) windows on a
         full key, 8 (+ 7 wide under msm_compact=2) on a compact one, 1 (the bases) on a plain one."""

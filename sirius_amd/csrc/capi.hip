@@ -246,6 +246,9 @@ private:
     unsigned workers_ = 0;
 };
 
+// finish() of a batched set on a plain key runs its members' chains of doublings over these workers (msm.h: set_parallel_for)
+const bool g_pool_lent = (msm::set_parallel_for([](size_t n, const std::function<void(size_t)> &fn) { HostPool::get().parallel_for(n, fn); }), true);
+
 int fail(int rc, const std::string &msg) {
     set_error(msg);
     return rc;
@@ -945,6 +948,17 @@ int srs_ck_plain_stats(const srs_ck *ck, uint64_t *out) {
         if (!k.plain) return;
         out[0] += k.stat_plain_fold_sets;
         out[1] += k.stat_plain_reductions;
+    });
+    return SRS_OK;
+}
+
+int srs_ck_plain_batch_stats(const srs_ck *ck, uint64_t *out) {
+    if (!ck || !out) return fail(SRS_ERR_INVALID, "srs_ck_plain_batch_stats: bad argument");
+    out[0] = out[1] = 0;
+    for_each_key(ck, [&](const msm::Key &k, const CkShard *) {
+        if (!k.plain) return;
+        out[0] += k.stat_plain_batch_sets;
+        out[1] += k.stat_plain_batch_msms;
     });
     return SRS_OK;
 }

@@ -7,6 +7,7 @@
 #include "tuning.h"
 
 #include <cstdlib>
+#include <functional>
 
 namespace srs {
 namespace msm {
@@ -79,6 +80,10 @@ inline bool expect_ovf_initial() { return tuning::get_or(tuning::MSM_EXPECT_OVF,
 // bucket set PER WINDOW, [windows][NBUCKET] points of run state (fold_buckets: 64 MiB, form 2: 32 MiB, allocated at the first folded set).
 // Form 2 (msm_plain = 2) is the same key in memory; its MSMs split the scalar as a compact key does (k = k1 + lambda k2, glv.cuh) and run 8
 // windows of two entries per scalar -- those of k2 flagged PAY_ENDO, level 0 gathers phi of the base -- so 8 bucket sets and 112 doublings.
+// A set of two or more non-empty MSMs (enqueue, batch > 1) runs as ONE flow whose linked segments are the (member, window) pairs, up to
+// 16 x 16 = 256 of them: one plan, one level 0, one bucket reduction and one landing copy for the set, the members' chains of doublings
+// over the host workers (set_parallel_for).  Tuning msm_plain_batch = 0, one non-empty member, a member above 2^20 scalars or 2^32 digit
+// slots in all keep the members one after the other (msm.hip: the batched plain flow).
 struct Key {
     int curve = 0;            // 0 bn256 G1, 1 grumpkin
     size_t len = 0;           // number of bases held by THIS rank
@@ -95,6 +100,8 @@ struct Key {
     // srs_ck_plain_stats (plain keys): sets that added their buckets into the running buckets (first and last included), and bucket
     // reductions of the plain flow -- one per unfolded MSM, one per folded commit
     uint64_t stat_plain_fold_sets = 0, stat_plain_reductions = 0;
+    // srs_ck_plain_batch_stats (plain keys): sets that ran the batched plain flow, and the MSMs (non-empty members) they carried
+    uint64_t stat_plain_batch_sets = 0, stat_plain_batch_msms = 0;
     uint64_t last_entries = 0;        // non-zero digits (= bucket additions) of the last commit that ran in slot mode (note_commit) ...
     uint64_t last_scalars = 0;        // ... and its scalars (both set by note_commit, both 0 when the commit had no slot-mode set): the density the next streamed commit's chunk cuts are chosen for
 
@@ -105,7 +112,7 @@ struct Key {
     // in slot mode, with its overflow kernels launched, and had this many MSMs (overflow_missed(), note_commit()); the plain flow produced
     // it (3 sums per WINDOW of every MSM, 16 or with plain_form == 2 eight of them, finish() weights the windows) for the MSMs of the mask --
     // the others were empty
-    struct Landing { bool wide = false, slot_mode = false, ovf_on = false; uint32_t batch = 0; bool plain = false; uint8_t plain_form = 0; uint32_t plain_ran = 0; } landing[LANDING_SLOTS];
+    struct Landing { bool wide = false, slot_mode = false, ovf_on = false; uint32_t batch = 0; bool plain = false; uint8_t plain_form = 0; uint32_t plain_ran = 0; bool plain_batched = false; } landing[LANDING_SLOTS];
     // running bucket sums of a chunked commit (enqueue(.., fold)) outside slot mode: [NBUCKET] points (enqueue_t), or on a plain key
     // [windows][NBUCKET] (the plain flow).  A plain key never takes enqueue_t and no other key the plain flow, so the two uses of the
     // pointer cannot meet.  Run state, not table: table_bytes() does not count it.
@@ -167,6 +174,10 @@ enum Fold { FOLD_NONE = 0, FOLD_FIRST = 1, FOLD_MIDDLE = 2, FOLD_LAST = 3 };
 bool enqueue(Key &k, const fe_t *const *scalars_dev, const uint32_t *n_host, const uint32_t *base_host, uint32_t batch, int is_mont,
              hipStream_t stream, uint32_t slot, Fold fold = FOLD_NONE);
 void finish(Key &k, uint32_t batch, uint32_t slot, bool launched, xyzz_t *result_host);
+// finish() of a batched set on a plain key runs the members' independent chains of doublings through this parallel-for (fn(0 .. n - 1),
+// returns when all are done) when one has been set: the C-ABI unit lends the library's host workers.  Unset: on the calling thread.
+using ParallelFor = void (*)(size_t n, const std::function<void(size_t)> &fn);
+void set_parallel_for(ParallelFor pf);
 void reserve(Key &k, uint32_t n_max, uint32_t batch);
 // Slot mode predicts per key whether a commit has parts beyond the slots (hot buckets: 0 / 1 / small witnesses) and launches the
 // overflow kernels only then.  After the stream has been synchronised: overflow_missed(slot) says that the set in `slot` HAD such parts

@@ -586,14 +586,30 @@ __global__ void SRS_KERNEL_BOUNDS(SORT_THREADS, 1)
 // (a witness of small values puts every entry into segment 0).  base[l][v] = first level-l part of segment v in the flat
 // thread space of level l (base[l][NSEG_W] = their number); in memory the parts of level l of segment v start at
 // base[l & 1][v] of ping (even l) / pong (odd l): a level never has more parts than the level two below it.
-struct Link {
-    uint32_t base[MAX_LEVELS + 1][NSEG_W + 1];
+// NS: the segment capacity.  NSEG_W for the wide flow and the single plain MSM; the batched plain flow links up to PLAIN_BATCH_SEG
+// segments, the (member, window) pairs of a set.  Every kernel that reads a link or the tile spaces of k_seg_scan carries NS with
+// NSEG_W as its default, so what the 16-segment flows launch is compiled as before and the batched flow has instantiations of its own.
+constexpr uint32_t PLAIN_BATCH_SEG = BATCH_ARGS * NWIN;      // 256
+template <uint32_t NS = NSEG_W>
+struct LinkT {
+    uint32_t base[MAX_LEVELS + 1][NS + 1];
 };
+using Link = LinkT<>;
+template <uint32_t NS = NSEG_W>
 __device__ __forceinline__ uint32_t link_segment(const uint32_t *__restrict__ base, uint32_t t) {   // base[v] <= t < base[v + 1]
-    uint32_t v = 0;
+    if constexpr (NS == NSEG_W) {
+        uint32_t v = 0;
 #pragma unroll
-    for (uint32_t u = 1; u < NSEG_W; ++u) v += (t >= base[u]) ? 1u : 0u;
-    return v;
+        for (uint32_t u = 1; u < NSEG_W; ++u) v += (t >= base[u]) ? 1u : 0u;
+        return v;
+    } else {                                  // largest v in [0, NS) with base[v] <= t (base is non-decreasing, base[0] = 0): log2(NS) loads
+        uint32_t lo = 0, hi = NS;
+        while (hi - lo > 1) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (base[mid] <= t) lo = mid; else hi = mid;
+        }
+        return lo;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -822,13 +838,119 @@ __global__ void SRS_KERNEL_BOUNDS(WIDE_THREADS, 1)
     }
 }
 
-// grid = NSEG_W: block v turns row v of tile_cnt into exclusive offsets into the grouped arrays (segment v starts where the
-// totals of segments < v end).  Block 0 also leaves seg_off[0..NSEG_W] and the tile space of the per-segment counting sort:
-// tile_base[v] = first workgroup of segment v when every segment is cut into tiles of `tile_g` entries.
+// The segment passes of a BATCH of MSMs on a plain key (the batched plain flow, host driver): the segment is the pair (member, window).
+// The descriptor travels as a kernel argument, like BatchDesc: the non-empty members of the set, packed; tile0[j] = first workgroup of
+// member j in the flat tile space (tile0[j] = T from the member count on), so a workgroup's WIDE_TILE scalars belong to ONE member.
+struct PlainBatchDesc {
+    const fe_t *ptr[BATCH_ARGS];
+    uint32_t n[BATCH_ARGS];
+    uint32_t base[BATCH_ARGS];
+    uint32_t tile0[BATCH_ARGS + 1];
+    int is_mont;
+};
+// Inside the workgroup this is k_seg_pass<PLAIN (, GLV)>: the member's windows are the 16 (8) per-wavefront LDS counters, each taken
+// once (twice) per wavefront and scalar; 48 KB of staging.  The global segment of window w is j * windows + w: row (segment) of
+// tile_cnt [segments][T], zeroed by the host -- a row only holds counts at its own member's tiles.  Payloads are those of the single
+// MSM (base[j] + i | sign << 31, | PAY_ENDO for the rows of k2), so level 0 is k_accum0 / k_accum0c unchanged.
+template <class C, bool GROUP, bool GLV>
+__global__ void SRS_KERNEL_BOUNDS(WIDE_THREADS, 1)
+    k_seg_pass_b(PlainBatchDesc bd, uint32_t *__restrict__ tile_cnt, uint32_t T, uint32_t *__restrict__ seg_total,
+                 uint16_t *__restrict__ gkey, uint32_t *__restrict__ gpay) {
+    constexpr int ND = NWIN;
+    constexpr uint32_t NWN = GLV ? NWIN_COMPACT : NWIN;          // windows = segments of a member
+    constexpr uint32_t NW = WIDE_THREADS / 64, STAGE = GROUP ? WIDE_TILE * ND : 1;
+    __shared__ uint32_t wc[NW][NWIN];
+    __shared__ uint32_t ss[NWIN + 1], goff[NWIN];
+    __shared__ uint16_t skey[STAGE];
+    __shared__ uint32_t spay[STAGE];
+    const uint32_t tile = blockIdx.x, wave = threadIdx.x >> 6;
+    uint32_t j = 0;                                               // the tile's member (workgroup-uniform)
+#pragma unroll
+    for (uint32_t u = 1; u < BATCH_ARGS; ++u) j += (tile >= bd.tile0[u]) ? 1u : 0u;
+    const WideDesc wd{bd.ptr[j], bd.n[j], bd.base[j], 0u, 1u, bd.is_mont};
+    const uint32_t mtile = tile - bd.tile0[j];
+    const size_t row0 = (size_t)j * NWN;                          // the member's first segment
+    if (threadIdx.x < NW * NWIN) (&wc[0][0])[threadIdx.x] = 0;
+    uint32_t code[WIDE_PER][ND];
+#pragma unroll
+    for (uint32_t k = 0; k < WIDE_PER; ++k) {
+        const uint32_t i = mtile * WIDE_TILE + k * WIDE_THREADS + threadIdx.x;
+        if constexpr (GLV) plain_glv_codes<C>(wd, i, code[k]); else plain_codes<C>(wd, i, code[k]);
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t k = 0; k < WIDE_PER; ++k) {
+#pragma unroll
+        for (int w = 0; w < ND; ++w) wave_take(&wc[wave][GLV ? w % NWIN_COMPACT : w], code[k][w] != 0xFFFFFFFFu);
+    }
+    __syncthreads();
+    if (threadIdx.x < NWN) {
+        const uint32_t v = threadIdx.x;
+        uint32_t tot = 0;
+        for (uint32_t w = 0; w < NW; ++w) tot += wc[w][v];
+        if (!GROUP) {
+            tile_cnt[(row0 + v) * T + tile] = tot;
+            if (tot) atomicAdd(&seg_total[row0 + v], tot);
+        } else {
+            ss[v + 1] = tot;
+            goff[v] = tile_cnt[(row0 + v) * T + tile];
+        }
+    }
+    if (!GROUP) return;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t run = 0;
+        for (uint32_t v = 0; v < NWN; ++v) {
+            const uint32_t c = ss[v + 1];
+            ss[v] = run;
+            run += c;
+        }
+        ss[NWN] = run;
+    }
+    __syncthreads();
+    if (threadIdx.x < NWN) {                     // counts -> first staging slot of (wavefront, window)
+        const uint32_t v = threadIdx.x;
+        uint32_t run = ss[v];
+        for (uint32_t w = 0; w < NW; ++w) {
+            const uint32_t c = wc[w][v];
+            wc[w][v] = run;
+            run += c;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t k = 0; k < WIDE_PER; ++k) {
+        const uint32_t i = mtile * WIDE_TILE + k * WIDE_THREADS + threadIdx.x;
+#pragma unroll
+        for (int w = 0; w < ND; ++w) {
+            const uint32_t c = code[k][w];
+            const uint32_t pos = wave_take(&wc[wave][GLV ? w % NWIN_COMPACT : w], c != 0xFFFFFFFFu);
+            if (c != 0xFFFFFFFFu) {              // (a staging slot below WIDE_TILE * ND: a tile holds at most that many entries)
+                skey[pos] = (uint16_t)(c & 0x7FFFu);
+                spay[pos] = ((wd.base | (GLV && w >= NWIN_COMPACT ? PAY_ENDO : 0u)) + i) | (c & 0x80000000u);
+            }
+        }
+    }
+    __syncthreads();
+    for (uint32_t v = 0; v < NWN; ++v) {
+        const uint32_t lo = ss[v], hi = ss[v + 1], g0 = goff[v];
+        for (uint32_t e = lo + threadIdx.x; e < hi; e += WIDE_THREADS) {
+            gkey[g0 + (e - lo)] = skey[e];
+            gpay[g0 + (e - lo)] = spay[e];
+        }
+    }
+}
+
+// grid = the segments in use (the 16-segment flows: NSEG_W): block v turns row v of tile_cnt into exclusive offsets into the grouped
+// arrays (segment v starts where the totals of segments < v end).  Block 0 also leaves seg_off[0..NS] and the tile space of the
+// per-segment counting sort: tile_base[v] = first workgroup of segment v when every segment is cut into tiles of `tile_g` entries.
+// The tile size aims at SORT_TARGET_BLOCKS - NSEG_W full tiles whatever NS; every segment with entries adds a partly filled one, so
+// k_hist_g / k_group_g need SORT_TARGET_BLOCKS - NSEG_W + (segments in use) workgroups.
+template <uint32_t NS = NSEG_W>
 __global__ void SRS_KERNEL_BOUNDS(1024, 1)
     k_seg_scan(uint32_t *__restrict__ tile_cnt, uint32_t T, const uint32_t *__restrict__ seg_total, uint32_t *__restrict__ seg_off,
-               uint32_t *__restrict__ tile_base /* [NSEG_W + 1], then the tile size */,
-               uint32_t *__restrict__ tile_base2 /* [NSEG_W + 1]: the same for the tiles of k_scatter2_g, then their size */,
+               uint32_t *__restrict__ tile_base /* [NS + 1], then the tile size */,
+               uint32_t *__restrict__ tile_base2 /* [NS + 1]: the same for the tiles of k_scatter2_g, then their size */,
                uint32_t small_tiles /* the launch of k_scatter2_g is sized for tiles of SORT_TILE2 / 4 (sets that may be sparse) */) {
     __shared__ uint32_t lds[64];
     const uint32_t v = blockIdx.x;
@@ -838,30 +960,30 @@ __global__ void SRS_KERNEL_BOUNDS(1024, 1)
         // tile size from the ACTUAL number of entries (zero digits are gone): <= SORT_TARGET_BLOCKS workgroups of 128 KiB LDS,
         // i.e. one round over the CUs, whatever the share of zeros
         uint32_t all = 0;
-        for (uint32_t u = 0; u < NSEG_W; ++u) all += seg_total[u];
+        for (uint32_t u = 0; u < NS; ++u) all += seg_total[u];
         uint32_t tile_g = (all + (SORT_TARGET_BLOCKS - NSEG_W) - 1) / (SORT_TARGET_BLOCKS - NSEG_W);
         tile_g = (tile_g + 1023u) & ~1023u;
         if (tile_g < SORT_TILE_MIN) tile_g = SORT_TILE_MIN;
-        tile_base[NSEG_W + 1] = tile_g;
+        tile_base[NS + 1] = tile_g;
         uint32_t run = 0, tr = 0;
-        for (uint32_t u = 0; u < NSEG_W; ++u) {
+        for (uint32_t u = 0; u < NS; ++u) {
             seg_off[u] = run;
             tile_base[u] = tr;
             run += seg_total[u];
             tr += (seg_total[u] + tile_g - 1) / tile_g;
         }
-        seg_off[NSEG_W] = run;
-        tile_base[NSEG_W] = tr;
+        seg_off[NS] = run;
+        tile_base[NS] = tr;
         // k_scatter2_g sorts a tile inside LDS only when it spans <= 2 sub-segments (S2_RANGE buckets); with < ~40 entries per bucket a tile
         // of SORT_TILE2 entries spans more and would go entry by entry through global atomics (the sets of a chunked commit, r05): smaller tiles
-        const uint32_t tile2 = (small_tiles && all / (NSEG_W * NBUCKET) < 40u) ? SORT_TILE2 / 4 : SORT_TILE2;
+        const uint32_t tile2 = (small_tiles && all / ((NS == NSEG_W ? NSEG_W : gridDim.x) * NBUCKET) < 40u) ? SORT_TILE2 / 4 : SORT_TILE2;
         uint32_t t2 = 0;
-        for (uint32_t u = 0; u < NSEG_W; ++u) {
+        for (uint32_t u = 0; u < NS; ++u) {
             tile_base2[u] = t2;
             t2 += (seg_total[u] + tile2 - 1) / tile2;
         }
-        tile_base2[NSEG_W] = t2;
-        tile_base2[NSEG_W + 1] = tile2;
+        tile_base2[NS] = t2;
+        tile_base2[NS + 1] = tile2;
     }
     uint32_t *row = tile_cnt + (size_t)v * T;
     uint32_t carry = 0;
@@ -877,23 +999,25 @@ __global__ void SRS_KERNEL_BOUNDS(1024, 1)
 
 // counting sort inside the segments, from the grouped (key, payload) arrays: same LDS histogram as k_hist / k_scatter,
 // one workgroup per tile of the flat tile space (tile_base)
+template <uint32_t NS = NSEG_W>
 __device__ __forceinline__ bool wide_tile(const uint32_t *__restrict__ seg_off, const uint32_t *__restrict__ tile_base,
                                           uint32_t &v, uint32_t &lo, uint32_t &hi) {
-    if (blockIdx.x >= tile_base[NSEG_W]) return false;
-    const uint32_t tile_g = tile_base[NSEG_W + 1];
-    v = link_segment(tile_base, blockIdx.x);
+    if (blockIdx.x >= tile_base[NS]) return false;
+    const uint32_t tile_g = tile_base[NS + 1];
+    v = link_segment<NS>(tile_base, blockIdx.x);
     lo = seg_off[v] + (blockIdx.x - tile_base[v]) * tile_g;
     hi = seg_off[v + 1];
     if (hi > lo + tile_g) hi = lo + tile_g;
     return true;
 }
 
+template <uint32_t NS = NSEG_W>
 __global__ void SRS_KERNEL_BOUNDS(SORT_THREADS, 1)
     k_hist_g(const uint16_t *__restrict__ gkey, const uint32_t *__restrict__ seg_off, const uint32_t *__restrict__ tile_base,
              uint32_t *__restrict__ count /* [NSEG_W][NBUCKET] */, uint32_t *__restrict__ tile_hist /* [SEG][gridDim.x] or nullptr */) {
     __shared__ uint32_t h[NBUCKET];
     uint32_t v, lo, hi;
-    if (!wide_tile(seg_off, tile_base, v, lo, hi)) return;
+    if (!wide_tile<NS>(seg_off, tile_base, v, lo, hi)) return;
     tile_histogram(h, gkey, lo, hi);
     uint32_t *cnt = count + (size_t)v * NBUCKET;
     for (uint32_t b = threadIdx.x; b < NBUCKET; b += blockDim.x) {
@@ -934,7 +1058,7 @@ __global__ void SRS_KERNEL_BOUNDS(1024, 1)
 
 // HOT0 (compact keys): sub-segment 0 of segment 0 holds the two top digit rows -- 1/7 of ALL entries, 3/4 of that segment's: its
 // counter is taken once per wavefront (wave_take).  An instantiation of its own; full keys launch k_group_g<false>, compiled as before.
-template <bool HOT0>
+template <bool HOT0, uint32_t NS = NSEG_W>
 __global__ void SRS_KERNEL_BOUNDS(SORT_THREADS, 1)
     k_group_g(const uint16_t *__restrict__ gkey, const uint32_t *__restrict__ gpay, const uint32_t *__restrict__ seg_off,
               const uint32_t *__restrict__ tile_base, const uint32_t *__restrict__ tile_hist, uint16_t *__restrict__ gkey2,
@@ -944,7 +1068,7 @@ __global__ void SRS_KERNEL_BOUNDS(SORT_THREADS, 1)
     __shared__ uint16_t skey[GRP_SUB];
     const uint32_t tid = threadIdx.x;
     uint32_t v, lo, hi;
-    if (!wide_tile(seg_off, tile_base, v, lo, hi)) return;
+    if (!wide_tile<NS>(seg_off, tile_base, v, lo, hi)) return;
     for (uint32_t sgm = tid; sgm < SEG; sgm += blockDim.x) cur[sgm] = tile_hist[(size_t)sgm * gridDim.x + blockIdx.x];
     for (uint32_t sub = lo; sub < hi; sub += GRP_SUB) {                 // workgroup-uniform
         for (uint32_t sgm = tid; sgm < SEG; sgm += blockDim.x) cnt[sgm] = 0;
@@ -990,6 +1114,7 @@ __global__ void SRS_KERNEL_BOUNDS(SORT_THREADS, 1)
     }
 }
 
+template <uint32_t NS = NSEG_W>
 __global__ void SRS_KERNEL_BOUNDS(SORT_THREADS, 2)
     k_scatter2_g(const uint16_t *__restrict__ gkey2, const uint32_t *__restrict__ gpay2, const uint32_t *__restrict__ seg_off,
                  const uint32_t *__restrict__ tile_base2, uint32_t *__restrict__ cursor /* [NSEG_W][NBUCKET], absolute */,
@@ -999,11 +1124,11 @@ __global__ void SRS_KERNEL_BOUNDS(SORT_THREADS, 2)
     __shared__ uint16_t skey[SORT_TILE2];
     const uint32_t tid = threadIdx.x;
     // XCD-aware tile mapping as in k_scatter2: every XCD sorts one contiguous eighth of the flat tile space
-    const uint32_t n_tiles = tile_base2[NSEG_W], per_xcd = (n_tiles + 7) / 8;
+    const uint32_t n_tiles = tile_base2[NS], per_xcd = (n_tiles + 7) / 8;
     if (blockIdx.x / 8 >= per_xcd) return;
     const uint32_t tile_id = (blockIdx.x % 8) * per_xcd + blockIdx.x / 8;
     if (tile_id >= n_tiles) return;
-    const uint32_t v = link_segment(tile_base2, tile_id), tile2 = tile_base2[NSEG_W + 1];
+    const uint32_t v = link_segment<NS>(tile_base2, tile_id), tile2 = tile_base2[NS + 1];
     const uint32_t lo = seg_off[v] + (tile_id - tile_base2[v]) * tile2;
     const uint32_t hi = lo + tile2 < seg_off[v + 1] ? lo + tile2 : seg_off[v + 1];
     if (lo >= hi) return;
@@ -1348,8 +1473,25 @@ __global__ void SRS_KERNEL_BOUNDS(PLAN_THREADS, 1)
 
 // `nseg`: the segments that k_plan ran for; the others (a plain key of form 2 populates 8 of the 16) own no part on any level, so that
 // base[l][nseg .. NSEG_W] all hold the number of parts and link_segment never names one of them
-__global__ void k_link(const uint32_t *__restrict__ plan, size_t plan_stride, int nlevels, Link *__restrict__ link, uint32_t nseg) {
+// NS > 64 (the batched plain flow): one thread per segment of capacity, block = NS, the scan goes through LDS.
+template <uint32_t NS = NSEG_W>
+__global__ void k_link(const uint32_t *__restrict__ plan, size_t plan_stride, int nlevels, LinkT<NS> *__restrict__ link, uint32_t nseg) {
     const uint32_t t = threadIdx.x;
+    if constexpr (NS > 64) {
+        __shared__ uint32_t lds[64];
+        for (int l = 0; l < nlevels; ++l) {                       // workgroup-uniform
+            uint32_t c = 0;
+            if (t < nseg) {
+                const uint32_t *pl = plan + (size_t)t * plan_stride;
+                if ((uint32_t)l < pl[plan_stride - 4]) c = pl[(size_t)(l + 1) * (NBUCKET + 1) + NBUCKET];
+            }
+            uint32_t total;
+            const uint32_t ex = block_exclusive_scan(c, lds, &total);
+            if (t < NS) link->base[l][t] = ex;
+            if (t == 0) link->base[l][NS] = total;
+        }
+        return;
+    }
     for (int l = 0; l < nlevels; ++l) {
         uint32_t c = 0;
         if (t < nseg) {
@@ -1375,9 +1517,10 @@ __global__ void k_link(const uint32_t *__restrict__ plan, size_t plan_stride, in
 // thread -> bucket map of level 0: tb[t] = b for tp0[b] <= t < tp0[b + 1].  k_accum0 used to find its bucket by a binary search
 // over the 2^15 prefix entries -- 15 DEPENDENT global loads (~15 us) in front of ~130 us of additions, in every thread.
 // One wavefront per bucket writes the (contiguous) range instead; the map is 2 bytes per thread.   grid = (NBUCKET / 4, batch)
+template <uint32_t NS = NSEG_W>
 __global__ void SRS_KERNEL_BOUNDS(256, 1)
     k_expand(const uint32_t *__restrict__ plan, size_t plan_stride, uint16_t *__restrict__ tb, size_t tb_stride,
-             const Link *__restrict__ link, uint32_t arr /* plan array holding the thread prefix: 1, or nlevels + 1 in slot mode */) {
+             const LinkT<NS> *__restrict__ link, uint32_t arr /* plan array holding the thread prefix: 1, or nlevels + 1 in slot mode */) {
     const uint32_t m = blockIdx.y, lane = threadIdx.x & 63u;
     const uint32_t b = blockIdx.x * 4 + (threadIdx.x >> 6);
     const uint32_t *tp = plan + (size_t)m * plan_stride + (size_t)arr * (NBUCKET + 1);
@@ -1470,17 +1613,17 @@ __device__ __forceinline__ xyzz29_t accumulate_part(const uint32_t *__restrict__
     return acc;
 }
 
-template <class C, bool COMPACT>
+template <class C, bool COMPACT, uint32_t NS = NSEG_W>
 __device__ __forceinline__ void accum0_thread(const uint32_t *__restrict__ sorted, size_t sorted_stride, const uint32_t *__restrict__ plan,
                                               size_t plan_stride, const uint16_t *__restrict__ tb, size_t tb_stride,
                                               const affine_t *__restrict__ table, xyzz_t *__restrict__ parts, size_t parts_stride, uint32_t l0,
-                                              const Link *__restrict__ link) {
+                                              const LinkT<NS> *__restrict__ link) {
     uint32_t m = blockIdx.y;
     uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     size_t slot;                                   // index of this thread's part (and map entry)
     if (link) {                                    // wide windows: flat thread space over the segments, offsets are absolute
-        if (t >= link->base[0][NSEG_W]) return;
-        m = link_segment(link->base[0], t);
+        if (t >= link->base[0][NS]) return;
+        m = link_segment<NS>(link->base[0], t);
         slot = t;
         t -= link->base[0][m];
     } else {
@@ -1500,20 +1643,20 @@ __device__ __forceinline__ void accum0_thread(const uint32_t *__restrict__ sorte
     const xyzz29_t acc = s < e ? accumulate_part<C, COMPACT>(src, s, e, table, nullptr) : E29::identity();
     parts[slot] = E29::pack(acc);                                // canonical R'-form: the later levels stay on the 29-bit multiplier
 }
-template <class C>
+template <class C, uint32_t NS = NSEG_W>
 __global__ void SRS_KERNEL_BOUNDS(ACC_THREADS, 1)
     k_accum0(const uint32_t *__restrict__ sorted, size_t sorted_stride, const uint32_t *__restrict__ plan,
              size_t plan_stride, const uint16_t *__restrict__ tb, size_t tb_stride, const affine_t *__restrict__ table,
-             xyzz_t *__restrict__ parts, size_t parts_stride, uint32_t l0, const Link *__restrict__ link) {
-    accum0_thread<C, false>(sorted, sorted_stride, plan, plan_stride, tb, tb_stride, table, parts, parts_stride, l0, link);
+             xyzz_t *__restrict__ parts, size_t parts_stride, uint32_t l0, const LinkT<NS> *__restrict__ link) {
+    accum0_thread<C, false, NS>(sorted, sorted_stride, plan, plan_stride, tb, tb_stride, table, parts, parts_stride, l0, link);
 }
 // the same for a compact key (entries flagged PAY_ENDO): a kernel of its own, so that the one full keys launch is compiled as before
-template <class C>
+template <class C, uint32_t NS = NSEG_W>
 __global__ void SRS_KERNEL_BOUNDS(ACC_THREADS, 1)
     k_accum0c(const uint32_t *__restrict__ sorted, size_t sorted_stride, const uint32_t *__restrict__ plan,
               size_t plan_stride, const uint16_t *__restrict__ tb, size_t tb_stride, const affine_t *__restrict__ table,
-              xyzz_t *__restrict__ parts, size_t parts_stride, uint32_t l0, const Link *__restrict__ link) {
-    accum0_thread<C, true>(sorted, sorted_stride, plan, plan_stride, tb, tb_stride, table, parts, parts_stride, l0, link);
+              xyzz_t *__restrict__ parts, size_t parts_stride, uint32_t l0, const LinkT<NS> *__restrict__ link) {
+    accum0_thread<C, true, NS>(sorted, sorted_stride, plan, plan_stride, tb, tb_stride, table, parts, parts_stride, l0, link);
 }
 
 // 64-lane exchange of an XYZZ point
@@ -1535,22 +1678,22 @@ __device__ __forceinline__ xyzz29_t shfl_down_point29(const xyzz29_t &p, unsigne
 //   many outputs  -> one lane per output (throughput-bound, every lane runs its own additions)
 //   few outputs   -> one QUAD per output (latency-bound tail: Ec::add_quad cuts the dependent chain 3.3x)
 // The grid is sized for the quad mode; in lane mode the surplus workgroups exit.
-template <class C>
+template <class C, uint32_t NS = NSEG_W>
 __global__ void SRS_KERNEL_BOUNDS(ACC_THREADS, 1)
     k_accum1(const xyzz_t *__restrict__ in, size_t in_stride, const uint32_t *__restrict__ plan,
              size_t plan_stride, int level, xyzz_t *__restrict__ out, size_t out_stride, uint32_t l1,
-             const Link *__restrict__ link, uint32_t quad_max) {
+             const LinkT<NS> *__restrict__ link, uint32_t quad_max) {
     uint32_t m = blockIdx.y;
     const uint32_t lin = blockIdx.x * blockDim.x + threadIdx.x;
     uint32_t t;
     bool quad;
     size_t in_off, out_off;
     if (link) {                                // wide windows: flat thread space of this level over the segments
-        const uint32_t n_all = link->base[level][NSEG_W];
+        const uint32_t n_all = link->base[level][NS];
         quad = n_all <= quad_max;
         t = quad ? (lin >> 2) : lin;
         if (t >= n_all) return;
-        m = link_segment(link->base[level], t);
+        m = link_segment<NS>(link->base[level], t);
         t -= link->base[level][m];
         in_off = link->base[(level - 1) & 1][m];
         out_off = link->base[level & 1][m];
@@ -1587,11 +1730,11 @@ __global__ void SRS_KERNEL_BOUNDS(ACC_THREADS, 1)
 
 // final level: one wavefront per bucket; lanes stride over the remaining parts, then a 6-step
 // shuffle tree; lane 0 stores the bucket.   grid = (NBUCKET / waves_per_block, batch)
-template <class C>
+template <class C, uint32_t NS = NSEG_W>
 __global__ void SRS_KERNEL_BOUNDS(FINAL_THREADS, 1)
     k_accum_final(const xyzz_t *__restrict__ ping, size_t ping_stride, const xyzz_t *__restrict__ pong,
                   size_t pong_stride, const uint32_t *__restrict__ plan, size_t plan_stride,
-                  xyzz_t *__restrict__ buckets, const Link *__restrict__ link) {
+                  xyzz_t *__restrict__ buckets, const LinkT<NS> *__restrict__ link) {
     uint32_t m = blockIdx.y;
     if (plan[(size_t)m * plan_stride + plan_stride - 3]) return;              // all buckets single: nothing to combine
     const uint32_t level = plan[(size_t)m * plan_stride + plan_stride - 4];   // levels actually run
@@ -1783,11 +1926,11 @@ __device__ __forceinline__ xyzz_t shfl_down_point_w(const xyzz_t &p, unsigned de
 // 16 quads of a wavefront combine by a shuffle tree (partner quad = 4 d lanes further).  A row (128 elements) is one
 // wavefront; a column (256 elements) is the two wavefronts of a workgroup, joined through LDS.
 // grid = (RED_ROWS / 2 + RED_COLS, batch), block = 128: workgroups < RED_ROWS / 2 do two rows, the others one column.
-template <class C>
+template <class C, uint32_t NS = NSEG_W>
 __global__ void SRS_KERNEL_BOUNDS(128, 1)
     k_rowcol(const xyzz_t *__restrict__ buckets, const xyzz_t *__restrict__ ping, size_t ping_stride,
              const xyzz_t *__restrict__ pong, size_t pong_stride, const uint32_t *__restrict__ plan, size_t plan_stride,
-             xyzz_t *__restrict__ rc /* [batch][ROWS + COLS] */, const Link *__restrict__ link, int from_buckets) {
+             xyzz_t *__restrict__ rc /* [batch][ROWS + COLS] */, const LinkT<NS> *__restrict__ link, int from_buckets) {
     constexpr uint32_t SER = 8;
     __shared__ xyzz_t half[1];
     const uint32_t m = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
@@ -1902,6 +2045,20 @@ __global__ void SRS_KERNEL_BOUNDS(256, 1)
         if (vl < d) x = E29::add_quad(x, o, q);
     }
     if (lane == 0) out[which] = E29::pack(x);
+}
+
+// the batched plain flow: the 3 sums of segment (j, w), packed by member, -> the landing layout, member slot[j] at point 3 NWIN slot[j]
+// (where the single flows land it: finish_t reads either the same way).   grid = 1
+struct LandMap {
+    uint8_t slot[BATCH_ARGS];
+};
+__global__ void SRS_KERNEL_BOUNDS(256, 1)
+    k_land_spread(const xyzz_t *__restrict__ in /* [members][nwin][3] */, xyzz_t *__restrict__ out /* [BATCH_ARGS][NWIN][3] */, LandMap map,
+                  uint32_t members, uint32_t nwin) {
+    for (uint32_t i = threadIdx.x; i < members * nwin * 3; i += blockDim.x) {
+        const uint32_t j = i / (3 * nwin), r = i % (3 * nwin);
+        out[3 * NWIN * (uint32_t)map.slot[j] + r] = in[i];
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2245,14 +2402,16 @@ static SlotBufs slot_layout(W &A, const SlotShape &h, uint32_t batch) {
     take_set_tail(A, h, batch, b);
     return b;
 }
-struct WideBufs {
+template <uint32_t NS = NSEG_W>
+struct WideBufsT {
     xyzz_t *d_out, *d_seg, *ping, *pong, *buckets, *rc;     // the MSM's 4 sums; 4 per segment; as in SetBufs, for the 16 segments together
     uint16_t *gkey, *gkey2, *tb;                   // grouped by segment (MSD pass), and again by sub-segment: the counting sort inside the
     uint32_t *gpay, *gpay2, *tile_cnt, *tile_hist; // segments in two passes through LDS (k_group_g + k_scatter2_g); their per-tile counts
     uint32_t *seg3;                                // seg_total, seg_off, tile_base, tile_base2: NSEG_W + 2 words each
     uint32_t *sorted, *count, *cursor, *plan;
-    Link *link;
+    LinkT<NS> *link;
 };
+using WideBufs = WideBufsT<>;
 template <class W>
 static WideBufs wide_layout(W &A, const WideShape &w) {
     WideBufs b;
@@ -2327,28 +2486,30 @@ static void sort_front(const Key &k, const SetShape &h, const SetBufs &b, const 
                    (uint32_t)k.len, h.tile);
     }
     if (!(h.two_pass && group_maps))
-        SRS_LAUNCH(k_expand, (NBUCKET / 4, batch), (256), 0, stream, (const uint32_t *)b.plan, h.plan_stride, b.tb, (size_t)h.cap0,
+        SRS_LAUNCH(k_expand<>, (NBUCKET / 4, batch), (256), 0, stream, (const uint32_t *)b.plan, h.plan_stride, b.tb, (size_t)h.cap0,
                    (const Link *)nullptr, arr);
 }
 
 // what the level kernels and the bucket reduction read of a set: its plan and the partial sums of the levels, ping (even levels) and
 // pong, with their strides per MSM of the batch -- 0 with a link: the segments of the wide flow share the buffers
-struct Parts {
+template <uint32_t NS = NSEG_W>
+struct PartsT {
     const uint32_t *plan; size_t plan_stride;
     xyzz_t *ping; size_t stride0;
     xyzz_t *pong; size_t stride1;
-    const Link *link;
+    const LinkT<NS> *link;
 };
+using Parts = PartsT<>;
 
 // accumulation levels 1 .. levels - 1 over ping / pong; `cap_inc`: what a level's worst-case part count adds to an eighth of the previous one
-template <class C>
-static void accum_levels(const Parts &p, const LevelShape &h, uint64_t cap_inc, uint32_t batch, hipStream_t stream) {
+template <class C, uint32_t NS = NSEG_W>
+static void accum_levels(const PartsT<NS> &p, const LevelShape &h, uint64_t cap_inc, uint32_t batch, hipStream_t stream) {
     xyzz_t *cur = p.ping, *nxt = p.pong;
     size_t cur_stride = p.stride0, nxt_stride = p.stride1;
     uint64_t cap = h.cap0;
     for (int level = 1; level < h.levels; ++level) {
         cap = cap / ACC_L1 + cap_inc;
-        SRS_LAUNCH((k_accum1<C>), (ceil_div(std::max<uint64_t>(cap, 4 * std::min<uint64_t>(cap, h.quad_max)), ACC_THREADS), batch),
+        SRS_LAUNCH((k_accum1<C, NS>), (ceil_div(std::max<uint64_t>(cap, 4 * std::min<uint64_t>(cap, h.quad_max)), ACC_THREADS), batch),
                    (ACC_THREADS), 0, stream, (const xyzz_t *)cur, cur_stride, p.plan, h.plan_stride, level, nxt, nxt_stride, (uint32_t)ACC_L1,
                    p.link, h.quad_max);
         std::swap(cur, nxt);
@@ -2359,10 +2520,10 @@ static void accum_levels(const Parts &p, const LevelShape &h, uint64_t cap_inc, 
 
 // bucket reduction of `nmsm` MSMs / segments: row and column sums (k_rowcol: of `from`, or with from_buckets == 0 of `from` plus what
 // the plan left in ping / pong), then their `sums` weighted totals per MSM into d_sums
-template <class C>
-static void reduce_buckets(const Parts &p, uint32_t nmsm, const xyzz_t *from, int from_buckets, xyzz_t *rc, uint32_t sums, xyzz_t *d_sums,
+template <class C, uint32_t NS = NSEG_W>
+static void reduce_buckets(const PartsT<NS> &p, uint32_t nmsm, const xyzz_t *from, int from_buckets, xyzz_t *rc, uint32_t sums, xyzz_t *d_sums,
                            hipStream_t stream) {
-    SRS_LAUNCH((k_rowcol<C>), (RED_ROWS / 2 + RED_COLS, nmsm), (128), 0, stream, from, (const xyzz_t *)p.ping, p.stride0,
+    SRS_LAUNCH((k_rowcol<C, NS>), (RED_ROWS / 2 + RED_COLS, nmsm), (128), 0, stream, from, (const xyzz_t *)p.ping, p.stride0,
                (const xyzz_t *)p.pong, p.stride1, p.plan, p.plan_stride, rc, p.link, from_buckets);
     SRS_LAUNCH((k_reduce_final<C>), (sums, nmsm), (RED_THREADS), 0, stream, (const xyzz_t *)rc, d_sums);
 }
@@ -2563,41 +2724,57 @@ struct SegKernels {
     decltype(&k_group_g<false>) group_g;
     decltype(&k_accum0<C>) accum0;
 };
-template <class C>
-static Parts segment_flow(const WideShape &w, const WideBufs &b, const WideDesc &wd, uint32_t table_stride, const SegKernels<C> &kn,
-                          const affine_t *table, uint32_t sums, hipStream_t stream, uint32_t nseg = NSEG_W, bool reduce = true) {
-    uint32_t *seg_total = b.seg3, *seg_off = b.seg3 + (NSEG_W + 2), *tile_base = b.seg3 + 2 * (NSEG_W + 2), *tile_base2 = b.seg3 + 3 * (NSEG_W + 2);
+// The flow for a segment capacity NS (NSEG_W, or PLAIN_BATCH_SEG in the batched plain flow, whose segments are the (member, window)
+// pairs of a set).  `front(group)` launches the segment pass over the scalars (group = false: counts, true: grouping) on w.T
+// workgroups; `scan_rows`: the rows of tile_cnt, one workgroup of k_seg_scan each; `units`: the scalars (the timing record of level 0).
+template <class C, uint32_t NS, class Front>
+static PartsT<NS> segment_flow_core(const WideShape &w, const WideBufsT<NS> &b, Front front, decltype(&k_group_g<false, NS>) group_g,
+                                    decltype(&k_accum0<C, NS>) accum0, uint64_t units, const affine_t *table, uint32_t sums,
+                                    hipStream_t stream, uint32_t nseg, uint32_t scan_rows, bool reduce) {
+    uint32_t *seg_total = b.seg3, *seg_off = b.seg3 + (NS + 2), *tile_base = b.seg3 + 2 * (NS + 2), *tile_base2 = b.seg3 + 3 * (NS + 2);
     // sort: segment counts -> offsets -> grouping (MSD pass), then the counting sort inside the segments
-    SRS_HIP_CHECK(hipMemsetAsync(seg_total, 0, (NSEG_W + 1) * sizeof(uint32_t), stream));
+    SRS_HIP_CHECK(hipMemsetAsync(seg_total, 0, (NS + 1) * sizeof(uint32_t), stream));
     SRS_HIP_CHECK(hipMemsetAsync(b.count, 0, (size_t)nseg * NBUCKET * sizeof(uint32_t), stream));
-    SRS_LAUNCH(kn.seg_count, (w.T), (WIDE_THREADS), 0, stream, wd, b.tile_cnt, w.T, seg_total, (uint16_t *)nullptr,
-               (uint32_t *)nullptr, table_stride);
+    front(false);
     const uint32_t small_tiles = (w.M >> 19) < 64 ? 1u : 0u, tile2_host = small_tiles ? SORT_TILE2 / 4 : SORT_TILE2;
-    SRS_LAUNCH(k_seg_scan, (NSEG_W), (1024), 0, stream, b.tile_cnt, w.T, (const uint32_t *)seg_total, seg_off, tile_base, tile_base2, small_tiles);
-    SRS_LAUNCH(kn.seg_group, (w.T), (WIDE_THREADS), 0, stream, wd, b.tile_cnt, w.T, seg_total, b.gkey, b.gpay, table_stride);
-    SRS_LAUNCH(k_hist_g, (w.tiles_g), (SORT_THREADS), 0, stream, (const uint16_t *)b.gkey, (const uint32_t *)seg_off,
+    SRS_LAUNCH(k_seg_scan<NS>, (scan_rows), (1024), 0, stream, b.tile_cnt, w.T, (const uint32_t *)seg_total, seg_off, tile_base, tile_base2, small_tiles);
+    front(true);
+    SRS_LAUNCH(k_hist_g<NS>, (w.tiles_g), (SORT_THREADS), 0, stream, (const uint16_t *)b.gkey, (const uint32_t *)seg_off,
                (const uint32_t *)tile_base, b.count, b.tile_hist);
     SRS_LAUNCH(k_plan, (nseg, w.levels + 1), (PLAN_THREADS), 0, stream, (const uint32_t *)b.count, b.cursor, b.plan, w.plan_stride, w.levels,
                w.l0_log, (uint32_t)ACC_L1_LOG, (const uint32_t *)seg_off);
     SRS_LAUNCH(k_scan_seg_g, (SEG, nseg), (1024), 0, stream, b.tile_hist, w.tiles_g, (const uint32_t *)tile_base, (const uint32_t *)b.plan,
                w.plan_stride);
-    SRS_LAUNCH(kn.group_g, (w.tiles_g), (SORT_THREADS), 0, stream, (const uint16_t *)b.gkey, (const uint32_t *)b.gpay, (const uint32_t *)seg_off,
+    SRS_LAUNCH(group_g, (w.tiles_g), (SORT_THREADS), 0, stream, (const uint16_t *)b.gkey, (const uint32_t *)b.gpay, (const uint32_t *)seg_off,
                (const uint32_t *)tile_base, (const uint32_t *)b.tile_hist, b.gkey2, b.gpay2);
-    // tiles of SORT_TILE2 entries cut per segment: at most M / SORT_TILE2 + NSEG_W of them; 8 x ceil(. / 8) workgroups (XCD mapping)
-    SRS_LAUNCH(k_scatter2_g, (8 * ceil_div(ceil_div(w.M, tile2_host) + NSEG_W, 8)), (SORT_THREADS), 0, stream, (const uint16_t *)b.gkey2,
+    // tiles of SORT_TILE2 entries cut per segment: at most M / SORT_TILE2 + (segments in use) of them; 8 x ceil(. / 8) workgroups (XCD mapping)
+    SRS_LAUNCH(k_scatter2_g<NS>, (8 * ceil_div(ceil_div(w.M, tile2_host) + scan_rows, 8)), (SORT_THREADS), 0, stream, (const uint16_t *)b.gkey2,
                (const uint32_t *)b.gpay2, (const uint32_t *)seg_off, (const uint32_t *)tile_base2, b.cursor, b.sorted);
-    SRS_LAUNCH(k_link, (1), (64), 0, stream, (const uint32_t *)b.plan, w.plan_stride, w.levels, b.link, nseg);
-    // from here on the 16 segments are ONE linked batch: no strides, the link says where a segment's parts start
-    const Parts p{b.plan, w.plan_stride, b.ping, 0, b.pong, 0, b.link};
-    SRS_LAUNCH(k_expand, (NBUCKET / 4, nseg), (256), 0, stream, p.plan, p.plan_stride, b.tb, (size_t)0, p.link, 1u);
-    SRS_LAUNCH_TIMED("msm_accum0", wd.n, kn.accum0, (ceil_div(w.cap0, ACC_THREADS)), (ACC_THREADS), 0, stream, (const uint32_t *)b.sorted,
+    SRS_LAUNCH(k_link<NS>, (1), (NS > 64 ? NS : 64), 0, stream, (const uint32_t *)b.plan, w.plan_stride, w.levels, b.link, nseg);
+    // from here on the segments are ONE linked batch: no strides, the link says where a segment's parts start
+    const PartsT<NS> p{b.plan, w.plan_stride, b.ping, 0, b.pong, 0, b.link};
+    SRS_LAUNCH(k_expand<NS>, (NBUCKET / 4, nseg), (256), 0, stream, p.plan, p.plan_stride, b.tb, (size_t)0, p.link, 1u);
+    SRS_LAUNCH_TIMED("msm_accum0", units, accum0, (ceil_div(w.cap0, ACC_THREADS)), (ACC_THREADS), 0, stream, (const uint32_t *)b.sorted,
                      (size_t)0, p.plan, p.plan_stride, (const uint16_t *)b.tb, (size_t)0, table, p.ping, (size_t)0,
                      1u << w.l0_log, p.link);
-    accum_levels<C>(p, w, (uint64_t)nseg * (NBUCKET + 1), 1, stream);
-    SRS_LAUNCH((k_accum_final<C>), (NBUCKET / (FINAL_THREADS / 64), nseg), (FINAL_THREADS), 0, stream, (const xyzz_t *)p.ping, p.stride0,
+    accum_levels<C, NS>(p, w, (uint64_t)nseg * (NBUCKET + 1), 1, stream);
+    SRS_LAUNCH((k_accum_final<C, NS>), (NBUCKET / (FINAL_THREADS / 64), nseg), (FINAL_THREADS), 0, stream, (const xyzz_t *)p.ping, p.stride0,
                (const xyzz_t *)p.pong, p.stride1, p.plan, p.plan_stride, b.buckets, p.link);
-    if (reduce) reduce_buckets<C>(p, nseg, b.buckets, 0, b.rc, sums, b.d_seg, stream);
+    if (reduce) reduce_buckets<C, NS>(p, nseg, b.buckets, 0, b.rc, sums, b.d_seg, stream);
     return p;
+}
+template <class C>
+static Parts segment_flow(const WideShape &w, const WideBufs &b, const WideDesc &wd, uint32_t table_stride, const SegKernels<C> &kn,
+                          const affine_t *table, uint32_t sums, hipStream_t stream, uint32_t nseg = NSEG_W, bool reduce = true) {
+    uint32_t *seg_total = b.seg3;
+    const auto front = [&](bool group) {
+        if (!group)
+            SRS_LAUNCH(kn.seg_count, (w.T), (WIDE_THREADS), 0, stream, wd, b.tile_cnt, w.T, seg_total, (uint16_t *)nullptr,
+                       (uint32_t *)nullptr, table_stride);
+        else
+            SRS_LAUNCH(kn.seg_group, (w.T), (WIDE_THREADS), 0, stream, wd, b.tile_cnt, w.T, seg_total, b.gkey, b.gpay, table_stride);
+    };
+    return segment_flow_core<C, NSEG_W>(w, b, front, kn.group_g, kn.accum0, wd.n, table, sums, stream, nseg, NSEG_W, reduce);
 }
 
 template <class C>
@@ -2618,8 +2795,9 @@ static bool enqueue_wide_t(Key &k, const fe_t *scalars_dev, uint32_t n, uint32_t
 // ---- the plain flow: ONE MSM of any size over a plain key (window 0 alone) ------------------------------------------------------------
 // The wide flow (segment_flow) with the WINDOW as the segment: k_seg_pass<PLAIN> groups the 16 n signed 16-bit digits by window, and from
 // k_hist_g to reduce_buckets the 16 windows are the 16 linked segments -- every entry gathers from k.table, the bases.  What leaves is 3 partial sums
-// per window, landed at point 3 NWIN m of the slot; finish_t weights the windows.  MSM m of a batch is one such flow after the other on
-// the stream: they share the arena in stream order (the caller has reserved it for the largest of them).
+// per window, landed at point 3 NWIN m of the slot; finish_t weights the windows.  A set of two or more MSMs runs as ONE such flow over
+// (member, window) segments (the batched plain flow, below); where it does not (use_plain_batch), MSM m of the set is one flow after the
+// other on the stream: they share the arena in stream order (the caller has reserved it for the largest of them).
 // Form 2 (msm_plain = 2, Key::plain_form): the same flow over the split scalar.  k_seg_pass<PLAIN, GLV> leaves 2 entries per scalar in
 // each of 8 windows, those of k2 flagged PAY_ENDO; level 0 is k_accum0c, which multiplies a flagged entry's x by beta; the stages from the
 // plan on run for 8 segments (segment_flow: nseg), 3 x 8 partial sums land and finish_t weights 8 windows.  A scalar has 16 digit rows in
@@ -2670,6 +2848,152 @@ static void enqueue_plain_t(Key &k, const fe_t *scalars_dev, uint32_t n, uint32_
     land(k, b.d_seg, 3 * (size_t)nwin, slot, stream, 3 * (size_t)NWIN * m);     // (the slot keeps room for 16 windows per MSM in either form)
 }
 
+// ---- the batched plain flow: the MSMs of ONE set as one linked flow ------------------------------------------------------------------
+// The segment is the pair (member j, window w) -- j counts the set's non-empty members --, global index j * windows + w, S = members x
+// windows of them (<= PLAIN_BATCH_SEG = 256).  k_seg_pass_b groups every member's digits by (member, window) in one launch over the flat
+// tile space of all members; from k_seg_scan on the S segments are what the 16 windows are to one MSM: one plan, one link, one level 0
+// and one set of levels over a flat thread space in which the parts of every member balance, one wave-level pass, one bucket reduction
+// of S segments, one landing copy.  All kernels that see more than 16 segments are the NS = PLAIN_BATCH_SEG instantiations.
+// A set stays sequential (enqueue_plain_t per member, as before): under tuning msm_plain_batch = 0, with one non-empty member, when
+// its 16 x sum n_m digit slots would not fit the 32-bit entry offsets, when it folds, and above PLAIN_BATCH_MAX_N scalars in a member.
+// Measured (profiles/plain_batch_ab.txt): the batched flow is faster at every member size of the sweep, 5 x 2^12 .. 5 x 2^20 and
+// 16 x 2^12, on both forms (by 38-50 % at 2^12, 17-23 % at 2^15, 7-10 % at 2^20), so no size inside the sweep stays sequential; sets
+// with a larger member were not measured and do.
+// Workspace: per segment 4 MiB of buckets, 4 MiB of level-0 parts and 4 MiB of level-1 parts (an empty bucket owns one part on every
+// level), the plan (0.25 MiB per level) and 0.25 MiB of counts and cursors, about 13 MiB -- 1.0 GiB for 5 members on form 1, 3.4 GiB
+// at 256 segments; part of the key's grow-only arena (reserve()), not of table_bytes().
+constexpr uint32_t PLAIN_BATCH_MAX_N = 1u << 20;
+struct PlainBatchShape : WideShape { uint32_t S; };
+// `n_sum`, `n_max`: all the scalars of the set and those of its largest member; T: tiles over all members
+static PlainBatchShape plain_batch_shape(uint64_t n_sum, uint32_t n_max, uint32_t T, uint32_t S) {
+    PlainBatchShape w;
+    w.S = S;
+    w.M = n_sum * NWIN;
+    w.quad_max = acc1_quad_max();
+    const uint64_t m_max = (uint64_t)n_max * NWIN;           // what a segment can hold: the part length and the levels follow the largest member,
+    w.l0_log = l0_log_for(m_max);                            // as in its own flow (worst case: its entries in one bucket of one segment)
+    w.levels = levels_for((m_max + (1ull << w.l0_log) - 1) >> w.l0_log);
+    w.plan_stride = (size_t)(w.levels + 1) * (NBUCKET + 1) + 4;
+    w.cap0 = (w.M >> w.l0_log) + (uint64_t)S * (NBUCKET + 1);        // an empty bucket owns one (identity) part on every level
+    w.cap1 = w.cap0 / ACC_L1 + (uint64_t)S * (NBUCKET + 1);
+    w.T = T;
+    w.tiles_g = SORT_TARGET_BLOCKS - NSEG_W + S;             // k_seg_scan: that many full tiles, one partly filled per segment
+    return w;
+}
+struct PlainBatchBufs : WideBufsT<PLAIN_BATCH_SEG> { xyzz_t *d_land; };
+template <class W>
+static PlainBatchBufs plain_batch_layout(W &A, const PlainBatchShape &w) {
+    constexpr uint32_t NS = PLAIN_BATCH_SEG;
+    PlainBatchBufs b;
+    b.d_out = nullptr;
+    b.d_land = A.template take<xyzz_t>(3 * (size_t)NWIN * BATCH_ARGS);
+    b.d_seg = A.template take<xyzz_t>(3 * (size_t)w.S);
+    b.gkey = A.template take<uint16_t>(w.M);
+    b.gpay = A.template take<uint32_t>(w.M);
+    b.sorted = A.template take<uint32_t>(w.M);
+    b.tile_cnt = A.template take<uint32_t>((size_t)w.S * w.T);
+    b.gkey2 = A.template take<uint16_t>(w.M);
+    b.gpay2 = A.template take<uint32_t>(w.M);
+    b.tile_hist = A.template take<uint32_t>((size_t)SEG * w.tiles_g);
+    b.seg3 = A.template take<uint32_t>(4 * (NS + 2));
+    b.link = A.template take<LinkT<NS>>(1);
+    b.count = A.template take<uint32_t>((size_t)w.S * NBUCKET);
+    b.cursor = A.template take<uint32_t>((size_t)w.S * NBUCKET);
+    b.plan = A.template take<uint32_t>(w.plan_stride * w.S);
+    b.ping = A.template take<xyzz_t>(w.cap0);
+    b.tb = A.template take<uint16_t>(w.cap0);
+    b.pong = A.template take<xyzz_t>(w.cap1);
+    b.buckets = A.template take<xyzz_t>((size_t)w.S * NBUCKET);
+    b.rc = A.template take<xyzz_t>((size_t)w.S * (RED_ROWS + RED_COLS));
+    return b;
+}
+static bool plain_batch_on() { return tuning::get_or(tuning::MSM_PLAIN_BATCH, 1) != 0; }
+// the members a batched set may carry at n_max scalars each: BATCH_ARGS, fewer where 16 x sum n_m would reach 2^32; 0: none
+static uint32_t plain_batch_members(uint32_t n_max, uint32_t batch) {
+    if (n_max == 0 || n_max > PLAIN_BATCH_MAX_N) return 0;
+    const uint64_t fit = ((1ull << 32) - 1) / ((uint64_t)NWIN * n_max);
+    const uint32_t b = (uint32_t)std::min<uint64_t>(std::min<uint32_t>(batch, BATCH_ARGS), fit);
+    return b >= 2 ? b : 0;
+}
+// what a batched set of up to `batch` members of up to n_max scalars needs: every size grows with the members and their scalars while
+// the part length stays; as in workspace_bytes_plain the largest n of every shorter part length is a candidate too
+static size_t workspace_bytes_plain_batch(uint32_t n_max, uint32_t batch, int form) {
+    size_t need = 0;
+    for (uint32_t n = std::min(n_max, PLAIN_BATCH_MAX_N); n;) {
+        const uint32_t b = plain_batch_members(n, batch);
+        if (b)
+            need = std::max(need, sized([&](auto &A) {
+                return plain_batch_layout(A, plain_batch_shape((uint64_t)b * n, n, b * ceil_div(n, WIDE_TILE), b * (uint32_t)plain_windows(form)));
+            }));
+        const uint32_t lg = l0_log_for((uint64_t)n * NWIN);
+        uint32_t lo = 1, hi = n;                               // smallest count with this part length
+        while (lo < hi) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if (l0_log_for((uint64_t)mid * NWIN) == lg) hi = mid; else lo = mid + 1;
+        }
+        n = lo - 1;
+    }
+    return need;
+}
+// does this set take the batched flow?  (read per set: tuning msm_plain_batch)
+static bool use_plain_batch(const uint32_t *n_host, uint32_t batch, Fold fold) {
+    if (fold != FOLD_NONE || !plain_batch_on()) return false;
+    uint32_t members = 0, n_max = 0;
+    uint64_t n_sum = 0;
+    for (uint32_t m = 0; m < batch; ++m) {
+        members += n_host[m] ? 1u : 0u;
+        n_max = std::max(n_max, n_host[m]);
+        n_sum += n_host[m];
+    }
+    return members >= 2 && n_max <= PLAIN_BATCH_MAX_N && n_sum * NWIN < (1ull << 32);
+}
+
+template <class C>
+static uint32_t enqueue_plain_batch_t(Key &k, const fe_t *const *scalars_dev, const uint32_t *n_host, const uint32_t *base_host, uint32_t batch,
+                                      int is_mont, hipStream_t stream, uint32_t slot) {
+    constexpr uint32_t NS = PLAIN_BATCH_SEG;
+    const bool glv = k.plain_form == 2;
+    const uint32_t nwin = (uint32_t)plain_windows(k.plain_form);
+    PlainBatchDesc bd{};
+    LandMap map{};
+    uint32_t members = 0, T = 0, n_max = 0, ran = 0, last = 0;
+    uint64_t n_sum = 0;
+    for (uint32_t m = 0; m < batch; ++m) {
+        if (n_host[m] == 0) continue;
+        bd.ptr[members] = scalars_dev[m];
+        bd.n[members] = n_host[m];
+        bd.base[members] = base_host ? base_host[m] : 0u;
+        bd.tile0[members] = T;
+        map.slot[members] = (uint8_t)m;
+        T += ceil_div(n_host[m], WIDE_TILE);
+        n_max = std::max(n_max, n_host[m]);
+        n_sum += n_host[m];
+        ran |= 1u << m;
+        last = m;
+        ++members;
+    }
+    for (uint32_t j = members; j <= BATCH_ARGS; ++j) bd.tile0[j] = T;
+    bd.is_mont = is_mont;
+    const uint32_t S = members * nwin;
+    const PlainBatchShape w = plain_batch_shape(n_sum, n_max, T, S);
+    const PlainBatchBufs b = carve(k.arena, [&](auto &A) { return plain_batch_layout(A, w); });
+    SRS_HIP_CHECK(hipMemsetAsync(b.tile_cnt, 0, (size_t)S * T * sizeof(uint32_t), stream));   // a row holds counts at its member's tiles alone
+    const auto front = [&](bool group) {
+        const auto pass = glv ? (group ? &k_seg_pass_b<C, true, true> : &k_seg_pass_b<C, false, true>)
+                              : (group ? &k_seg_pass_b<C, true, false> : &k_seg_pass_b<C, false, false>);
+        SRS_LAUNCH(pass, (T), (WIDE_THREADS), 0, stream, bd, b.tile_cnt, T, b.seg3, group ? b.gkey : (uint16_t *)nullptr,
+                   group ? b.gpay : (uint32_t *)nullptr);
+    };
+    segment_flow_core<C, NS>(w, b, front, &k_group_g<false, NS>, glv ? &k_accum0c<C, NS> : &k_accum0<C, NS>, n_sum, k.table, 3, stream, S, S,
+                             true);
+    SRS_LAUNCH(k_land_spread, (1), (256), 0, stream, (const xyzz_t *)b.d_seg, b.d_land, map, members, nwin);
+    land(k, b.d_land, 3 * (size_t)NWIN * (last + 1), slot, stream);
+    k.stat_plain_reductions += members;
+    ++k.stat_plain_batch_sets;
+    k.stat_plain_batch_msms += members;
+    return ran;
+}
+
 // a set of <= BATCH_ARGS MSMs on a plain key.  Returns false when every MSM is empty (nothing was launched).
 template <class C>
 static bool enqueue_plain_set_t(Key &k, const fe_t *const *scalars_dev, const uint32_t *n_host, const uint32_t *base_host, uint32_t batch,
@@ -2677,18 +3001,27 @@ static bool enqueue_plain_set_t(Key &k, const fe_t *const *scalars_dev, const ui
     uint32_t n_max = 0, ran = 0;
     for (uint32_t m = 0; m < batch; ++m) n_max = std::max(n_max, n_host[m]);
     if (n_max == 0) return false;
-    k.arena.reserve(workspace_bytes_plain(n_max));          // before the first launch: growing it between two flows would free memory in use
-    for (uint32_t m = 0; m < batch; ++m) {
-        if (n_host[m] == 0) continue;
-        enqueue_plain_t<C>(k, scalars_dev[m], n_host[m], base_host ? base_host[m] : 0u, is_mont, stream, slot, m, fold);
-        ran |= 1u << m;
+    const bool batched = use_plain_batch(n_host, batch, fold);
+    if (batched) {
+        ran = enqueue_plain_batch_t<C>(k, scalars_dev, n_host, base_host, batch, is_mont, stream, slot);
+    } else {
+        k.arena.reserve(workspace_bytes_plain(n_max));      // before the first launch: growing it between two flows would free memory in use
+        for (uint32_t m = 0; m < batch; ++m) {
+            if (n_host[m] == 0) continue;
+            enqueue_plain_t<C>(k, scalars_dev[m], n_host[m], base_host ? base_host[m] : 0u, is_mont, stream, slot, m, fold);
+            ran |= 1u << m;
+        }
     }
+    k.landing[slot].plain_batched = batched;
     k.landing[slot].wide = false;
     k.landing[slot].plain = true;
     k.landing[slot].plain_form = k.plain_form;
     k.landing[slot].plain_ran = ran;
     return true;
 }
+
+static ParallelFor g_parallel_for = nullptr;
+void set_parallel_for(ParallelFor pf) { g_parallel_for = pf; }
 
 // host end of enqueue_t, after `stream` has been synchronised:  S = RED_COLS * (2 A' + Z) + B  (10 group operations per MSM)
 template <class C>
@@ -2718,14 +3051,22 @@ static void finish_t(Key &k, uint32_t batch, uint32_t slot, bool launched, xyzz_
         return Ec<C>::add(a, two[at + 1]);
     };
     if (plain) {                                                // sum_w 2^(16 w) R_w as a Horner chain from the top window: 240 doublings, 15 additions
-        for (uint32_t m = 0; m < batch; ++m) {                  // (form 2: 8 windows, 112 doublings, 8 additions)
+        const auto chain = [&](size_t m) {                      // (form 2: 8 windows, 112 doublings, 8 additions)
             xyzz_t acc = Ec<C>::identity();
             for (int w = nwin - 1; w >= 0 && (k.landing[slot].plain_ran >> m & 1u); --w) {
                 for (int d = 0; d < WBITS && w != nwin - 1; ++d) acc = Ec<C>::dbl(acc);
                 acc = Ec<C>::add(acc, bucket_sum(3 * ((size_t)NWIN * m + w)));
             }
             result_host[m] = acc;
+        };
+        // the chains of the members do not depend on one another.  Behind a batched set they are the largest serial item left
+        // (0.2-0.5 ms each on one core), so they go over the host workers the library keeps (set_parallel_for); tuning
+        // msm_plain_batch = 2 keeps them on the calling thread (the A/B of profiles/plain_batch_ab.txt)
+        if (k.landing[slot].plain_batched && g_parallel_for && tuning::get_or(tuning::MSM_PLAIN_BATCH, 1) != 2) {
+            g_parallel_for(batch, chain);
+            return;
         }
+        for (uint32_t m = 0; m < batch; ++m) chain(m);
         return;
     }
     for (uint32_t m = 0; m < batch; ++m) result_host[m] = bucket_sum(3 * (size_t)m);
@@ -2781,8 +3122,10 @@ void finish(Key &k, uint32_t batch, uint32_t slot, bool launched, xyzz_t *result
     if (k.curve == 0) finish_t<Bn256>(k, batch, slot, launched, result_host); else finish_t<Grumpkin>(k, batch, slot, launched, result_host);
 }
 void reserve(Key &k, uint32_t n_max, uint32_t batch) {
-    if (k.plain) {                           // the MSMs of a batch run one after the other in one arena
-        k.arena.reserve(workspace_bytes_plain(n_max));
+    if (k.plain) {                           // one arena: for the flow of one MSM (a sequential set runs its members one after the other) and,
+        size_t b = workspace_bytes_plain(n_max);             // unless tuning msm_plain_batch = 0 keeps every set sequential, for the batched flow
+        if (batch > 1 && plain_batch_on()) b = std::max(b, workspace_bytes_plain_batch(n_max, batch, k.plain_form));
+        k.arena.reserve(b);
         return;
     }
     size_t b = use_wide(k, n_max, batch) ? std::max(workspace_bytes_wide(n_max, wide_digits(k.compact)), workspace_bytes(n_max, batch))

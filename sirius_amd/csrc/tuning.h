@@ -31,6 +31,7 @@ enum Id : int {
     PG_JIT_WAVES,       // 0 auto | 1, 2 (developer): the waves per SIMD the run-time compiled ProtoGalaxy leaf kernels are bounded for (__launch_bounds__(128, n)); read when the unit is compiled
     MSM_PLAIN,          // 0 a key with window tables | 1 plain key: the bases alone (1/16 of the full key's HBM, no table to build); every MSM weights its 16 window sums by doublings | 2 the same key, MSMs over the split scalar (endomorphism): 8 window sums; read when a key is created, refused together with msm_compact
     MSM_PLAIN_FOLD,     // 1 a streamed commit on a plain key folds its chunks' buckets into one running bucket set per window (one reduction, landing and host chain per commit) | 0 every chunk a whole MSM; read when a streamed commit starts
+    MSM_PLAIN_BATCH,    // 1 a set of two or more MSMs on a plain key runs as one linked flow, its (member, window) pairs the segments (the arena holds that flow's workspace: INTEGRATION.md 6) | 0 the members one after the other, no additional workspace | 2 (developer) as 1 with the members' host chains on the calling thread; read when a set is enqueued
     N_TUNABLES
 };
 

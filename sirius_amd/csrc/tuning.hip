@@ -9,7 +9,7 @@ namespace tuning {
 
 static std::atomic<int64_t> g_val[N_TUNABLES];
 static const char *const kNames[N_TUNABLES] = {"msm_sort", "msm_l0", "msm_wide", "msm_wide_min", "msm_slots", "msm_slot_log", "msm_expect_ovf",
-                                               "msm_quad_max", "commit_chunks", "pg_f_eval", "pg_g_fft", "jit_always", "no_jit", "msm_compact", "pg_compat_tree", "pg_jit_force", "pg_jit_waves", "msm_plain", "msm_plain_fold"};
+                                               "msm_quad_max", "commit_chunks", "pg_f_eval", "pg_g_fft", "jit_always", "no_jit", "msm_compact", "pg_compat_tree", "pg_jit_force", "pg_jit_waves", "msm_plain", "msm_plain_fold", "msm_plain_batch"};
 static struct Init {
     Init() { for (auto &v : g_val) v.store(UNSET, std::memory_order_relaxed); }
 } g_init;

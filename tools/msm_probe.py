@@ -77,7 +77,7 @@ for n in sizes:
 if batch:
     vs = [scalars(batch[1], "uniform") for _ in range(batch[0])]
     txt, _ = timed(lambda: ck.commit_batch(vs))
-    print(f"batch {batch[0]} x {batch[1]} uniform {txt}  tag={tag}", flush=True)
+    print(f"batch {batch[0]} x {batch[1]} uniform {txt}  {ck.plain_batch_stats()}  tag={tag}", flush=True)
 if streamed:
     import numpy as np
     sys.path.insert(0, os.path.join(ROOT, "tests"))
